@@ -4,7 +4,10 @@
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N>1 it is launched
 by ``torch.distributed.run`` (one rank per GPU, RCCL).  W untimed warmup steps, then EXACTLY
 K timed steps bracketed by barrier + ``torch.cuda.synchronize()``; the max time over ranks is
-used and rank 0 prints ONE JSON line.
+used and rank 0 prints ONE JSON line.  ``--dump-outputs DIR`` also writes what the last timed step
+computed (its metrics, the updated parameters and BatchNorm statistics) as ``DIR/<name>.npy``; weights
+and batches are seeded, so two builds run with the same arguments can be compared array for array.
+``--full`` is where every measurement beyond the headline figure goes; a plain run has none.
 
 The timed step is the full PyTorchTrial training step as run by
 ``determined_amd.pytorch`` (``examples/resnet50/model_def.py:ResNet50Trial.train_batch``):
@@ -25,13 +28,17 @@ sys.path.insert(0, ROOT)
 # torch.backends.cudnn.benchmark searches): a fresh box reuses it instead of re-searching every
 # conv solver on every rank during warm-up.
 _MIOPEN_DB = os.path.join(ROOT, "determined_amd", "benchmarks", "miopen_db")
-if int(os.environ.get("WORLD_SIZE", "1")) > 1 and "MIOPEN_USER_DB_PATH" not in os.environ:
-    # one private copy per rank: N processes never write the same find-db files concurrently
+if "MIOPEN_USER_DB_PATH" not in os.environ:
+    # one private copy per process, removed at exit: MIOpen appends to its user db, so the committed
+    # files stay as they are (every run starts from the same db), and the N processes of a
+    # multi-GPU run never write the same find-db files concurrently
+    import atexit
     import shutil
     import tempfile
 
     _priv = os.path.join(tempfile.gettempdir(), f"damd_miopen_db_rank{os.environ.get('LOCAL_RANK', '0')}_{os.getpid()}")
     shutil.copytree(_MIOPEN_DB, _priv, dirs_exist_ok=True)
+    atexit.register(shutil.rmtree, _priv, ignore_errors=True)
     _MIOPEN_DB = _priv
 os.environ.setdefault("MIOPEN_USER_DB_PATH", _MIOPEN_DB)
 
@@ -64,7 +71,36 @@ def parse() -> argparse.Namespace:
     # samples/s, profiles/resnet50_b2048_finddb_vs_immediate_1gpu.txt)
     p.add_argument("--conv-benchmark", type=int, default=0,
                    help="1: let MIOpen search for the fastest conv solvers (torch.backends.cudnn.benchmark)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed to DIR/<name>.npy")
+    # a plain run does only what the headline figure needs (set up, warm up, time, report); every
+    # further measurement belongs behind --full.  Today there is none: the flag is accepted so that
+    # callers can pass it to every run alike
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline figure (none at present)")
     return p.parse_args()
+
+
+# at most this many elements of one dumped array (float32: 16 MiB), far below the 64 MB allowed in all
+_DUMP_MAX_ELEMS = 4 * 2**20
+
+
+def dump_outputs(outdir: str, outputs: dict) -> None:
+    """Write each tensor of ``outputs`` as ``outdir/<name>.npy`` (float32, or float64 where it is one).
+    An array above ``_DUMP_MAX_ELEMS`` elements is cut down to that many, drawn at positions that
+    depend only on its size (seeded CPU generator): two builds write the same positions."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > _DUMP_MAX_ELEMS:
+            g = torch.Generator()
+            g.manual_seed(0)
+            idx = torch.randint(t.numel(), (_DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu()
+        np.save(os.path.join(outdir, f"{name}.npy"), t.numpy())
 
 
 def main() -> int:
@@ -93,6 +129,7 @@ def main() -> int:
 
     from determined_amd.benchmarks.resnet50 import build_step
 
+    torch.manual_seed(0)  # the same weights and batches from run to run (the harness seeds itself alike)
     if world > 1 and os.environ.get("DAMD_BENCH_STREAM_K", "0") != "1":
         # Stream-K tiles hand partial sums between blocks of one launch (spin-waits with a time-out);
         # with RCCL kernels co-resident on some CUs that hand-off is the one place a collective can
@@ -159,6 +196,9 @@ def main() -> int:
     if rank == 0:
         print(f"[bench] peak GPU memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB", file=sys.stderr, flush=True)
     loss = float(state["last_loss"]()) if "last_loss" in state else float("nan")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, state["outputs"]())
+        print(f"[bench] wrote the last step's outputs to {a.dump_outputs}", file=sys.stderr, flush=True)
     if rank == 0 and os.environ.get("DAMD_TUNE_DUMP"):  # per-layer kernel choices (A/B analysis)
         from determined_amd.ops.conv import tuned_choices
 

@@ -56,7 +56,8 @@ def harness_step(batch: int, variant: str, bucket_mb: float, device: torch.devic
     def step() -> None:
         i = state["i"]
         ctx._current_batch_idx = i
-        state["metrics"].append(ctrl._train_batch(pool[i % len(pool)], 0, i))
+        state["last"] = ctrl._train_batch(pool[i % len(pool)], 0, i)
+        state["metrics"].append(state["last"])
         ctrl.state.batches_trained += 1
         state["i"] = i + 1
         if len(state["metrics"]) == 100:  # reporting period: one aggregation + D2H per 100 batches
@@ -90,6 +91,13 @@ def harness_step(batch: int, variant: str, bucket_mb: float, device: torch.devic
             m.zero_grad(set_to_none=True)
         torch.cuda.synchronize()
 
+    def outputs() -> Dict[str, torch.Tensor]:
+        """The last step's metrics as the controller returned them, and the model it updated."""
+        from determined_amd.benchmarks.resnet50 import step_outputs
+
+        return step_outputs(state["last"], trial.model)
+
     state["last_loss"] = last_loss
     state["tune"] = tune
+    state["outputs"] = outputs
     return step, state

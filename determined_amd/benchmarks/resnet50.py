@@ -79,4 +79,17 @@ def build_step(batch: int = 256, variant: str = "bf16_master", bucket_mb: float 
         state["loss"] = loss.detach()
 
     state["last_loss"] = lambda: state["loss"].item()
+    state["outputs"] = lambda: step_outputs({"loss": state["loss"]}, model)
     return step, state
+
+
+def step_outputs(metrics: Dict[str, Any], model: nn.Module) -> Dict[str, torch.Tensor]:
+    """What one training step hands back: its metrics (``metric_<name>``) and the model it updated
+    (``params``: every parameter, flattened in ``named_parameters`` order; ``bn_running_stats``:
+    every floating-point buffer alike), as fp32 tensors."""
+    out = {f"metric_{k}": v.detach().float().reshape(-1) for k, v in metrics.items() if isinstance(v, torch.Tensor)}
+    out["params"] = torch.cat([p.detach().float().reshape(-1) for _, p in model.named_parameters()])
+    bufs = [b.detach().float().reshape(-1) for _, b in model.named_buffers() if b.is_floating_point()]
+    if bufs:
+        out["bn_running_stats"] = torch.cat(bufs)
+    return out

@@ -1,5 +1,5 @@
-"""Replay the reference's expconf test corpus (schemas/test_cases/v0/*.yaml, read as data with
-yaml.safe_load) against determined_amd.config._schema.
+"""Replay the reference's expconf test corpus (schemas/test_cases/v0/*.yaml, stored unchanged under
+tests/golden/expconf_cases_v0 and read as data with yaml.safe_load) against determined_amd.config._schema.
 
 Each reference case holds a config under ``case`` and any of: ``sane_as`` (schemas it must pass),
 ``sanity_errors`` ({schema: [regex, ...]} -- every regex must match one rendered error),
@@ -18,7 +18,7 @@ import yaml
 
 from determined_amd.config import _schema as S
 
-CASE_DIR = "/root/reference/schemas/test_cases/v0"
+CASE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "expconf_cases_v0")
 FILES = sorted(glob.glob(os.path.join(CASE_DIR, "*.yaml")))
 
 # Cases whose expectations depend on behaviour this implementation intentionally does not reproduce.
@@ -66,7 +66,6 @@ def _check_errors(errors, patterns, what):
         assert any(re.search(p, e) for e in errors), f"no {what} error matches {p!r}; got {errors}"
 
 
-@pytest.mark.skipif(not FILES, reason="reference schema corpus not present")
 @pytest.mark.parametrize("case", _cases())
 def test_reference_case(case):
     if case["name"] in SKIPS:
@@ -93,8 +92,7 @@ def test_reference_case(case):
 
 def test_corpus_coverage():
     """The corpus is replayed nearly whole: at most the documented SKIPS are left out."""
-    if not FILES:
-        pytest.skip("reference schema corpus not present")
+    assert FILES, f"no corpus files under {CASE_DIR}"
     total = sum(len(yaml.safe_load(open(f)) or []) for f in FILES)
     assert total >= 130 and len(SKIPS) <= total - 120
 
