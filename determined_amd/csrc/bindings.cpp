@@ -317,6 +317,31 @@ const GroupHyper* hyper_ptr(const c10::optional<at::Tensor>& t) {
 
 int64_t hyper_bytes() { return sizeof(GroupHyper); }
 
+// The update kernels exist for: an fp32 parameter with any gradient dtype and an optional 16-bit
+// copy (whose format must be the gradient's when the gradient is 16-bit), or a 16-bit parameter
+// with a gradient of its own dtype or fp32 and no copy.  Anything else has no kernel: refuse it
+// (before any launch, whatever the table holds) instead of running the nearest instantiation.
+void check_opt_dtypes(const char* who, int64_t p_dtype, int64_t g_dtype, int64_t has_lp) {
+  TORCH_CHECK(p_dtype >= 0 && p_dtype <= 2 && g_dtype >= 0 && g_dtype <= 2 && has_lp >= 0 && has_lp <= 2, who,
+              ": dtype codes must be 0 (fp32), 1 (bf16) or 2 (fp16); got p_dtype=", p_dtype, " g_dtype=", g_dtype,
+              " has_lp=", has_lp);
+  // the range check above comes first: the messages below name a code that is not 1 as fp16
+  if (p_dtype == 0) {
+    TORCH_CHECK(has_lp == 0 || g_dtype == 0 || g_dtype == has_lp, who, ": no kernel for a ",
+                g_dtype == 1 ? "bf16" : "fp16", " gradient with a ", has_lp == 1 ? "bf16" : "fp16",
+                " low-precision copy");
+  } else {
+    TORCH_CHECK(has_lp == 0, who, ": a low-precision copy needs an fp32 master parameter");
+    TORCH_CHECK(g_dtype == 0 || g_dtype == p_dtype, who, ": no kernel for a ", p_dtype == 1 ? "bf16" : "fp16",
+                " parameter with a ", g_dtype == 1 ? "bf16" : "fp16", " gradient");
+  }
+}
+
+void check_grad_dtype(const char* who, int64_t g_dtype) {
+  TORCH_CHECK(g_dtype >= 0 && g_dtype <= 2, who, ": gradient dtype code must be 0 (fp32), 1 (bf16) or 2 (fp16); got ",
+              g_dtype);
+}
+
 // the kernels of later steps (also graph replays) read these hyperparameters from `dst`
 void store_hyper(at::Tensor dst, std::vector<double> lr, std::vector<double> wd, std::vector<double> b1,
                  std::vector<double> b2, std::vector<double> eps, std::vector<int64_t> flag) {
@@ -329,6 +354,7 @@ void adam_step(const at::Tensor& table, std::vector<double> lr, std::vector<doub
                const c10::optional<at::Tensor>& scale, const c10::optional<at::Tensor>& found_inf,
                const at::Tensor& step, bool maximize, int64_t p_dtype, int64_t g_dtype, int64_t has_lp,
                const c10::optional<at::Tensor>& hyper_dev) {
+  check_opt_dtypes("adam_step", p_dtype, g_dtype, has_lp);
   TORCH_CHECK(step.scalar_type() == at::kFloat && step.is_cuda(), "step must be a float32 GPU scalar");
   const GroupHyper h = make_hyper(lr, wd, b1, b2, eps, decoupled);
   damd_adam_launch(table.data_ptr(), n_chunks_of(table), h, hyper_ptr(hyper_dev), opt_fptr(scale),
@@ -340,6 +366,7 @@ void sgd_step(const at::Tensor& table, std::vector<double> lr, std::vector<doubl
               std::vector<double> damp, std::vector<int64_t> nesterov, const c10::optional<at::Tensor>& scale,
               const c10::optional<at::Tensor>& found_inf, const at::Tensor& step, bool maximize, int64_t p_dtype,
               int64_t g_dtype, int64_t has_lp, bool momentum, const c10::optional<at::Tensor>& hyper_dev) {
+  check_opt_dtypes("sgd_step", p_dtype, g_dtype, has_lp);
   TORCH_CHECK(step.scalar_type() == at::kFloat && step.is_cuda(), "step must be a float32 GPU scalar");
   std::vector<double> eps(lr.size(), 0.0);
   const GroupHyper h = make_hyper(lr, wd, mom, damp, eps, nesterov);
@@ -349,6 +376,7 @@ void sgd_step(const at::Tensor& table, std::vector<double> lr, std::vector<doubl
 }
 
 void l2norm_partial(const at::Tensor& table, at::Tensor partial, int64_t g_dtype) {
+  check_grad_dtype("l2norm_partial", g_dtype);
   const int n = n_chunks_of(table);
   TORCH_CHECK(partial.scalar_type() == at::kFloat && partial.numel() >= n, "partial buffer too small");
   damd_l2norm_partial_launch(table.data_ptr(), n, partial.data_ptr<float>(), g_dtype, cur_stream());
@@ -370,6 +398,7 @@ void step_incr(at::Tensor step, const c10::optional<at::Tensor>& found_inf) {
 }
 
 void scale_grads(const at::Tensor& table, const at::Tensor& scale, int64_t g_dtype) {
+  check_grad_dtype("scale_grads", g_dtype);
   damd_scale_launch(table.data_ptr(), n_chunks_of(table), scale.data_ptr<float>(), g_dtype, cur_stream());
 }
 

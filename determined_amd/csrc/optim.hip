@@ -43,6 +43,18 @@ struct GroupHyper {
   int32_t flag[kMaxGroups];  // adam: 1=decoupled (AdamW); sgd: 1=nesterov
 };
 
+// The 16-bit copy of a master must be the rounding of the fp32 value that was stored.  Left alone,
+// the compiler folds the update's last fma and the fp16 conversion into one v_fma_mixlo_f16, which
+// rounds the exact fma once and so differs from the cast of the stored master at double-rounding
+// ties.  An empty asm keeps the stored value opaque to that fold (no instruction is emitted).
+__device__ __forceinline__ float stored(float x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+__device__ __forceinline__ float4 stored(float4 v) {
+  return make_float4(stored(v.x), stored(v.y), stored(v.z), stored(v.w));
+}
+
 // ----------------------------------------------------------------------------- AdamW
 template <typename PT, typename GT, bool LP, typename LT = bf16_t>
 __global__ void __launch_bounds__(kOptThreads)
@@ -98,7 +110,7 @@ adam_kernel(const MTChunk* __restrict__ chunks, GroupHyper hp, const GroupHyper*
       Vec4<PT>::st(p + i, pv);
       *reinterpret_cast<float4*>(m + i) = mv;
       *reinterpret_cast<float4*>(v + i) = vv;
-      if (LP) Vec4<LT>::st(plp + i, pv);
+      if (LP) Vec4<LT>::st(plp + i, stored(pv));
     }
   } else {
     for (int i = threadIdx.x; i < c.n; i += kOptThreads) {
@@ -106,7 +118,7 @@ adam_kernel(const MTChunk* __restrict__ chunks, GroupHyper hp, const GroupHyper*
       const float pv = upd(Elem<PT>::ld(p, i), Elem<GT>::ld(g, i), mv, vv);
       Elem<PT>::st(p, i, pv);
       m[i] = mv; v[i] = vv;
-      if (LP) Elem<LT>::st(plp, i, pv);
+      if (LP) Elem<LT>::st(plp, i, stored(pv));
     }
   }
 }
@@ -135,7 +147,8 @@ sgd_kernel(const MTChunk* __restrict__ chunks, GroupHyper hp, const GroupHyper* 
 
   auto upd = [&](float pv, float gv, float& bv) -> float {
     gv = gv * gs + wd * pv;
-    if (MOM) {
+    // a momentum-free group inside a momentum launch ignores dampening, as torch.optim.SGD does
+    if (MOM && mom != 0.f) {
       bv = first ? gv : mom * bv + (1.f - damp) * gv;
       gv = nesterov ? gv + mom * bv : bv;
     }
@@ -157,7 +170,7 @@ sgd_kernel(const MTChunk* __restrict__ chunks, GroupHyper hp, const GroupHyper* 
       pv.w = upd(pv.w, gv.w, bv.w);
       Vec4<PT>::st(p + i, pv);
       if (MOM) *reinterpret_cast<float4*>(buf + i) = bv;
-      if (LP) Vec4<LT>::st(plp + i, pv);
+      if (LP) Vec4<LT>::st(plp + i, stored(pv));
     }
   } else {
     for (int i = threadIdx.x; i < c.n; i += kOptThreads) {
@@ -165,7 +178,7 @@ sgd_kernel(const MTChunk* __restrict__ chunks, GroupHyper hp, const GroupHyper* 
       const float pv = upd(Elem<PT>::ld(p, i), Elem<GT>::ld(g, i), bv);
       Elem<PT>::st(p, i, pv);
       if (MOM) buf[i] = bv;
-      if (LP) Elem<LT>::st(plp, i, pv);
+      if (LP) Elem<LT>::st(plp, i, stored(pv));
     }
   }
 }

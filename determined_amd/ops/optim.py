@@ -162,7 +162,8 @@ class _FusedBase(torch.optim.Optimizer):
                     self._init_state(p, state)
                 master = self._master(p, state)
                 tgt = master if master is not None else p
-                key = (p.device, batch, _dcode(tgt), _dcode(p.grad), master is not None)
+                # the copy's dtype is part of the key: one launch writes one 16-bit format
+                key = (p.device, batch, _dcode(tgt), _dcode(p.grad), _dcode(p) if master is not None else 0)
                 b = buckets.setdefault(key, {"p": [], "g": [], "s0": [], "s1": [], "lp": [], "grp": []})
                 b["p"].append(tgt)
                 b["g"].append(p.grad)
