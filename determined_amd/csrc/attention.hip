@@ -29,6 +29,10 @@
 //   and made the backward atomic-bound; recomputing S and dP costs two extra MFMA tiles per
 //   block pair and no atomics.
 //
+// Grouped-query attention (K / V with Hkv heads, G = H / Hkv query heads per K/V head): the
+//   forward and dQ kernels index K / V by h / G and keep one group's workgroups on one XCD
+//   (wg_map); dK/dV is attn_bwd_gqa_kernel, which sums the group's heads in its accumulators.
+//
 // Strides are in elements for (batch, head, token); the head dimension must be contiguous.
 //
 // Key padding (BERT-style batches): an optional byte mask km[b][key] (row stride kms, rows padded to
@@ -94,7 +98,7 @@ __device__ __forceinline__ uint32_t md_seed(const KeyMaskDrop& md) {
 struct FwdArgs {
   const bf16_t* q; const bf16_t* k; const bf16_t* v; bf16_t* o; float* lse;
   Strides sq, sk, sv, so;
-  int H, T;
+  int H, T, G;  // G = H / Hkv query heads per K/V head
   float scale_log2;  // softmax scale * log2(e)
   KeyMaskDrop md;
 };
@@ -104,6 +108,8 @@ struct BwdArgs {
   const float* lse; const float* delta; float* dq_acc; bf16_t* dk; bf16_t* dv;
   Strides sq, sk, sv, sdo, sdk, sdv;
   int H, T;
+  int G, S;          // grouped-query dK/dV: group size, workgroups per group (head split)
+  float* part;       // S > 1: fp32 partials [2 (dk, dv)][S][B * Hkv][T][D]
   float scale, scale_log2;
   KeyMaskDrop md;
 };
@@ -210,12 +216,19 @@ struct Stage {
 // its own 4 MB L2); with the natural order a head's K/V (or Q/dO) tiles were fetched by workgroups
 // on all 8 XCDs -- from the Infinity Cache / HBM, at a latency the one-tile-ahead prefetch cannot
 // cover.  j = 0 is the heaviest block under a causal mask (dispatched first across the chip).
-__device__ __forceinline__ void wg_map(int nblk, int& j, int& bh) {
-  const int L = blockIdx.x, BH = gridDim.x / nblk;
-  if ((BH & 7) == 0) {
-    const int xcd = L & 7, slot = L >> 3, per = BH >> 3;
+// Grouped-query attention (G = H / Hkv > 1 query heads read one K/V head): the unit that stays on
+// one XCD is the (batch, kv head) group -- its G heads x nblk workgroups all read the same K/V
+// tiles, which the per-head map would pull into eight L2s.  Needs B*Hkv % 8 == 0, else the plain
+// order.  G = 1 is the per-head map unchanged.  The gain of the grouped map over the per-head
+// one for G > 1 is unmeasured: profiles/attention_gqa_probe.txt times the kernels with this map
+// against the MHA kernels on repeated K/V, not one map against the other.
+__device__ __forceinline__ void wg_map(int nblk, int G, int& j, int& bh) {
+  const int L = blockIdx.x, BH = gridDim.x / nblk, BKV = BH / G;
+  if ((BKV & 7) == 0) {
+    const int xcd = L & 7, slot = L >> 3, per = (BKV >> 3) * G;  // (kv group, head) pairs per XCD
     j = slot / per;
-    bh = (slot - j * per) * 8 + xcd;
+    const int rem = slot - j * per, grp = rem / G;
+    bh = (grp * 8 + xcd) * G + (rem - grp * G);
   } else {
     j = L / BH;
     bh = L - j * BH;
@@ -234,13 +247,13 @@ __global__ void __launch_bounds__(kThreads) attn_fwd_kernel(FwdArgs a) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
   const int T = a.T, nkb = (T + kBlk - 1) / kBlk, nqb = (T + kFwdRows - 1) / kFwdRows;
   int j, bhi;
-  wg_map(nqb, j, bhi);
+  wg_map(nqb, a.G, j, bhi);
   const int qb = CAUSAL ? nqb - 1 - j : j;
   const int h = bhi % a.H, b = bhi / a.H;
   const int q0 = qb * kFwdRows, qw = q0 + w * 16 * kQT;  // first query row of this wave
   const bf16_t* Qp = a.q + b * a.sq.b + h * a.sq.h;
-  const bf16_t* Kp = a.k + b * a.sk.b + h * a.sk.h;
-  const bf16_t* Vp = a.v + b * a.sv.b + h * a.sv.h;
+  const bf16_t* Kp = a.k + b * a.sk.b + (h / a.G) * a.sk.h;
+  const bf16_t* Vp = a.v + b * a.sv.b + (h / a.G) * a.sv.h;
   const uint8_t* KMp = a.md.km ? a.md.km + b * a.md.kms : nullptr;
   const uint32_t bh32 = static_cast<uint32_t>(b * a.H + h);
 
@@ -407,6 +420,60 @@ __global__ void __launch_bounds__(256) attn_delta_kernel(const bf16_t* __restric
   if (row < rows && part == 0) delta[row] = acc;
 }
 
+// One 64-query block of the dK/dV pass for a wave's 16 keys: the block's Q / dO tiles and its
+// lse (x log2 e) / delta rows are staged in LDS, the K / V fragments of the keys stay in registers,
+// dk / dv accumulate.  bh = b*H + (query head): the dropout counter.
+template <int D, bool CAUSAL, bool DROP>
+__device__ __forceinline__ void bwd_block(const BwdArgs& a, const bf16_t* Qs, const bf16_t* dOs, const float* lse2,
+                                          const float* dl, const s8 (&kf)[D / 32], const s8 (&vf)[D / 32],
+                                          f4 (&dk)[D / 16], f4 (&dv)[D / 16], uint32_t bh, int q0, int k0, int mykey,
+                                          bool kvalid, bool has_km) {
+  constexpr int RP = kLdsStride(D);
+  const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
+  const int T = a.T;
+  const bool need_mask = (k0 + kBlk > T) || (CAUSAL && q0 < k0 + kBlk) || has_km;
+  // two halves of 32 queries: S / dP -> P / dS of one half feed its dV / dK MFMAs right away
+  // (half the live P / dS registers: <= 128 VGPRs at D = 64, 4 waves per SIMD)
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2) {
+    f4 P[2], dS[2];
+#pragma unroll
+    for (int hq = 0; hq < 2; ++hq) {
+      const int qt = 2 * s2 + hq;
+      f4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ds = 0; ds < D / 32; ++ds) {
+        const s8 qa = *reinterpret_cast<const s8*>(Qs + (qt * 16 + c) * RP + ds * 32 + 8 * g);
+        const s8 oa = *reinterpret_cast<const s8*>(dOs + (qt * 16 + c) * RP + ds * 32 + 8 * g);
+        sacc = mfma(qa, kf[ds], sacc);
+        dpacc = mfma(oa, vf[ds], dpacc);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int ql = qt * 16 + 4 * g + r;
+        float p = ex2(fmaf(sacc[r], a.scale_log2, -lse2[ql]));
+        if (need_mask) p = (!kvalid || (CAUSAL && mykey > q0 + ql)) ? 0.f : p;
+        if constexpr (DROP) {
+          const bool keep = drop_keep(md_seed(a.md), a.md.thresh, bh, q0 + ql, mykey);
+          P[hq][r] = keep ? p * a.md.inv_keep : 0.f;  // dV uses the dropped, rescaled probabilities
+          dS[hq][r] = p * ((keep ? dpacc[r] * a.md.inv_keep : 0.f) - dl[ql]);
+        } else {
+          P[hq][r] = p;
+          dS[hq][r] = p * (dpacc[r] - dl[ql]);
+        }
+      }
+    }
+    // dV^T += dO^T . P ; dK^T += Q^T . dS   (k = 32 queries per step, permuted order)
+    const s8 pb = pack_pair(P[0], P[1]);
+    const s8 sb = pack_pair(dS[0], dS[1]);
+#pragma unroll
+    for (int dt = 0; dt < D / 16; ++dt) {
+      dv[dt] = mfma(tr_pair(dOs, RP, s2 * 32 + 4 * g, s2 * 32 + 16 + 4 * g, dt * 16, c), pb, dv[dt]);
+      dk[dt] = mfma(tr_pair(Qs, RP, s2 * 32 + 4 * g, s2 * 32 + 16 + 4 * g, dt * 16, c), sb, dk[dt]);
+    }
+  }
+}
+
 template <int D, bool CAUSAL, bool DROP>
 __global__ void __launch_bounds__(kThreads) attn_bwd_kernel(BwdArgs a) {
   constexpr int RP = kLdsStride(D);
@@ -417,7 +484,7 @@ __global__ void __launch_bounds__(kThreads) attn_bwd_kernel(BwdArgs a) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
   const int T = a.T, nblk = (T + kBlk - 1) / kBlk;
   int kb, bhi;
-  wg_map(nblk, kb, bhi);  // causal: the lowest key blocks see the most query blocks
+  wg_map(nblk, 1, kb, bhi);  // causal: the lowest key blocks see the most query blocks
   const int h = bhi % a.H, b = bhi / a.H;
   const int k0 = kb * kBlk;
   const bf16_t* Qp = a.q + b * a.sq.b + h * a.sq.h;
@@ -464,47 +531,8 @@ __global__ void __launch_bounds__(kThreads) attn_bwd_kernel(BwdArgs a) {
       ost.load(dOp, a.sdo.t, q0 + kBlk, T);
     }
 
-    const bool need_mask = (k0 + kBlk > T) || (CAUSAL && q0 < k0 + kBlk) || KMp != nullptr;
-    // two halves of 32 queries: S / dP -> P / dS of one half feed its dV / dK MFMAs right away
-    // (half the live P / dS registers: <= 128 VGPRs at D = 64, 4 waves per SIMD)
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      f4 P[2], dS[2];
-#pragma unroll
-      for (int hq = 0; hq < 2; ++hq) {
-        const int qt = 2 * s2 + hq;
-        f4 sacc = {0.f, 0.f, 0.f, 0.f}, dpacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ds = 0; ds < D / 32; ++ds) {
-          const s8 qa = *reinterpret_cast<const s8*>(Qs + (qt * 16 + c) * RP + ds * 32 + 8 * g);
-          const s8 oa = *reinterpret_cast<const s8*>(dOs + (qt * 16 + c) * RP + ds * 32 + 8 * g);
-          sacc = mfma(qa, kf[ds], sacc);
-          dpacc = mfma(oa, vf[ds], dpacc);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int ql = qt * 16 + 4 * g + r;
-          float p = ex2(fmaf(sacc[r], a.scale_log2, -lse2[ql]));
-          if (need_mask) p = (!kvalid || (CAUSAL && mykey > q0 + ql)) ? 0.f : p;
-          if constexpr (DROP) {
-            const bool keep = drop_keep(md_seed(a.md), a.md.thresh, static_cast<uint32_t>(bh), q0 + ql, mykey);
-            P[hq][r] = keep ? p * a.md.inv_keep : 0.f;  // dV uses the dropped, rescaled probabilities
-            dS[hq][r] = p * ((keep ? dpacc[r] * a.md.inv_keep : 0.f) - dl[ql]);
-          } else {
-            P[hq][r] = p;
-            dS[hq][r] = p * (dpacc[r] - dl[ql]);
-          }
-        }
-      }
-      // dV^T += dO^T . P ; dK^T += Q^T . dS   (k = 32 queries per step, permuted order)
-      const s8 pb = pack_pair(P[0], P[1]);
-      const s8 sb = pack_pair(dS[0], dS[1]);
-#pragma unroll
-      for (int dt = 0; dt < D / 16; ++dt) {
-        dv[dt] = mfma(tr_pair(dOs, RP, s2 * 32 + 4 * g, s2 * 32 + 16 + 4 * g, dt * 16, c), pb, dv[dt]);
-        dk[dt] = mfma(tr_pair(Qs, RP, s2 * 32 + 4 * g, s2 * 32 + 16 + 4 * g, dt * 16, c), sb, dk[dt]);
-      }
-    }
+    bwd_block<D, CAUSAL, DROP>(a, Qs, dOs, lse2, dl, kf, vf, dk, dv, static_cast<uint32_t>(bh), q0, k0, mykey, kvalid,
+                               KMp != nullptr);
   }
   if (mykey < T) {
     bf16_t* dKp = a.dk + b * a.sdk.b + h * a.sdk.h + static_cast<int64_t>(mykey) * a.sdk.t;
@@ -523,11 +551,142 @@ __global__ void __launch_bounds__(kThreads) attn_bwd_kernel(BwdArgs a) {
   }
 }
 
+// dK/dV of grouped-query attention (G = H / Hkv > 1).  A workgroup owns 64 keys of one (batch,
+// kv head): its K / V fragments are loaded once, and ONE flat loop runs over (query head of the
+// group, query block) with dk / dv accumulating in the same fp32 registers -- the group sum
+// happens in the accumulators (no atomics, no [B, H, T, D] gradient, no reduction pass), and K / V
+// are read once per group instead of once per query head.  The one-block-ahead Q / dO register
+// prefetch runs across head boundaries: the loads of the next head's first block are issued
+// before the MFMAs of the current head's last block, so the pipeline drains once, not G times.
+// lse / delta / the dropout counter follow the query head of the iteration.
+// Head split (a.S > 1, small grids): workgroup part s of S takes the heads [s*G/S, (s+1)*G/S) of
+// the group (uneven when S does not divide G; S <= G, so no part is empty) and writes fp32
+// partials a.part[dk|dv][s][b*Hkv + hkv][key][D]; attn_gqa_sum_kernel adds them in part order.
+template <int D, bool CAUSAL, bool DROP>
+__global__ void __launch_bounds__(kThreads) attn_bwd_gqa_kernel(BwdArgs a) {
+  constexpr int RP = kLdsStride(D);
+  __shared__ __attribute__((aligned(16))) bf16_t Qs[kBlk * RP];
+  __shared__ __attribute__((aligned(16))) bf16_t dOs[kBlk * RP];
+  __shared__ float lse2[kBlk], dl[kBlk];
+
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
+  const int T = a.T, nblk = (T + kBlk - 1) / kBlk, Hkv = a.H / a.G;
+  int kb, unit;
+  wg_map(nblk, 1, kb, unit);  // unit = (b*Hkv + hkv)*S + part: the blocks of one part share its heads' Q / dO
+  const int part = unit % a.S, bkv = unit / a.S;
+  const int hkv = bkv % Hkv, b = bkv / Hkv;
+  const int hg0 = part * a.G / a.S, hg1 = (part + 1) * a.G / a.S;  // heads of the group, [hg0, hg1)
+  const int k0 = kb * kBlk;
+  const bf16_t* Qb = a.q + b * a.sq.b;
+  const bf16_t* dOb = a.dout + b * a.sdo.b;
+  const bf16_t* Kp = a.k + b * a.sk.b + hkv * a.sk.h;
+  const bf16_t* Vp = a.v + b * a.sv.b + hkv * a.sv.h;
+  const int mykey = k0 + w * 16 + c;
+  const uint8_t* KMp = a.md.km ? a.md.km + b * a.md.kms : nullptr;
+  const bool kvalid = mykey < T && (KMp == nullptr || KMp[mykey] != 0);
+
+  s8 kf[D / 32], vf[D / 32];
+#pragma unroll
+  for (int ds = 0; ds < D / 32; ++ds) {
+    s8 x = {0, 0, 0, 0, 0, 0, 0, 0}, y = x;
+    if (mykey < T) {
+      x = *reinterpret_cast<const s8*>(Kp + static_cast<int64_t>(mykey) * a.sk.t + ds * 32 + 8 * g);
+      y = *reinterpret_cast<const s8*>(Vp + static_cast<int64_t>(mykey) * a.sv.t + ds * 32 + 8 * g);
+    }
+    kf[ds] = x;
+    vf[ds] = y;
+  }
+  f4 dk[D / 16], dv[D / 16];
+#pragma unroll
+  for (int dt = 0; dt < D / 16; ++dt) dk[dt] = dv[dt] = f4{0.f, 0.f, 0.f, 0.f};
+
+  const int qb0 = CAUSAL ? kb : 0;
+  int h = hkv * a.G + hg0;  // query head of the iteration
+  const int h_end = hkv * a.G + hg1;
+  Stage<D, kBlk> qst, ost;
+  qst.load(Qb + h * a.sq.h, a.sq.t, qb0 * kBlk, T);
+  ost.load(dOb + h * a.sdo.h, a.sdo.t, qb0 * kBlk, T);
+  for (int qb = qb0; h < h_end;) {
+    const int q0 = qb * kBlk;
+    const int64_t bh = static_cast<int64_t>(b) * a.H + h;
+    __syncthreads();
+    qst.store(Qs);
+    ost.store(dOs);
+    if (threadIdx.x < kBlk) {
+      const int q = q0 + threadIdx.x;
+      lse2[threadIdx.x] = q < T ? a.lse[bh * T + q] * kLog2e : INFINITY;
+      dl[threadIdx.x] = q < T ? a.delta[bh * T + q] : 0.f;
+    }
+    __syncthreads();
+    // next iteration: the following query block, or the first block of the next head
+    const bool last = qb + 1 == nblk;
+    const int nh = last ? h + 1 : h, nqb = last ? qb0 : qb + 1;
+    if (nh < h_end) {
+      qst.load(Qb + nh * a.sq.h, a.sq.t, nqb * kBlk, T);
+      ost.load(dOb + nh * a.sdo.h, a.sdo.t, nqb * kBlk, T);
+    }
+    bwd_block<D, CAUSAL, DROP>(a, Qs, dOs, lse2, dl, kf, vf, dk, dv, static_cast<uint32_t>(bh), q0, k0, mykey, kvalid,
+                               KMp != nullptr);
+    h = nh;
+    qb = nqb;
+  }
+  if (mykey >= T) return;
+  if (a.S == 1) {
+    bf16_t* dKp = a.dk + b * a.sdk.b + hkv * a.sdk.h + static_cast<int64_t>(mykey) * a.sdk.t;
+    bf16_t* dVp = a.dv + b * a.sdv.b + hkv * a.sdv.h + static_cast<int64_t>(mykey) * a.sdv.t;
+#pragma unroll
+    for (int dt = 0; dt < D / 16; ++dt) {
+      s4 kv, vv;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        kv[r] = bfs(dk[dt][r] * a.scale);
+        vv[r] = bfs(dv[dt][r]);
+      }
+      *reinterpret_cast<s4*>(dKp + dt * 16 + 4 * g) = kv;
+      *reinterpret_cast<s4*>(dVp + dt * 16 + 4 * g) = vv;
+    }
+  } else {
+    const int64_t plane = static_cast<int64_t>(gridDim.x / (nblk * a.S)) * T * D;  // B*Hkv*T*D
+    float* pk = a.part + (part * plane + (static_cast<int64_t>(bkv) * T + mykey) * D);
+    float* pv = pk + a.S * plane;
+#pragma unroll
+    for (int dt = 0; dt < D / 16; ++dt) {
+      *reinterpret_cast<f4*>(pk + dt * 16 + 4 * g) = dk[dt] * a.scale;
+      *reinterpret_cast<f4*>(pv + dt * 16 + 4 * g) = dv[dt];
+    }
+  }
+}
+
+// dk / dv = sum over the S head-split partials, part 0 first (a fixed order: the same result for
+// the same S on every run), written as bf16 through the dK / dV strides.  One thread per 4 columns.
+__global__ void __launch_bounds__(256) attn_gqa_sum_kernel(const float* __restrict__ part, int S, bf16_t* dk, Strides sdk,
+                                                           bf16_t* dv, Strides sdv, int Hkv, int T, int D,
+                                                           int64_t plane) {
+  const int64_t i = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) * 4;
+  if (i >= plane) return;
+  f4 k = *reinterpret_cast<const f4*>(part + i), v = *reinterpret_cast<const f4*>(part + S * plane + i);
+  for (int s = 1; s < S; ++s) {
+    k += *reinterpret_cast<const f4*>(part + s * plane + i);
+    v += *reinterpret_cast<const f4*>(part + (S + s) * plane + i);
+  }
+  const int d = static_cast<int>(i % D), t = static_cast<int>(i / D % T);
+  const int64_t bkv = i / D / T;
+  const int hkv = static_cast<int>(bkv % Hkv), b = static_cast<int>(bkv / Hkv);
+  s4 kv, vv;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    kv[r] = bfs(k[r]);
+    vv[r] = bfs(v[r]);
+  }
+  *reinterpret_cast<s4*>(dk + b * sdk.b + hkv * sdk.h + static_cast<int64_t>(t) * sdk.t + d) = kv;
+  *reinterpret_cast<s4*>(dv + b * sdv.b + hkv * sdv.h + static_cast<int64_t>(t) * sdv.t + d) = vv;
+}
+
 struct DqArgs {
   const bf16_t* q; const bf16_t* k; const bf16_t* v; const bf16_t* dout;
   const float* lse; const float* delta; bf16_t* dq;
   Strides sq, sk, sv, sdo, sdq;
-  int H, T;
+  int H, T, G;
   float scale, scale_log2;
   KeyMaskDrop md;
 };
@@ -542,14 +701,14 @@ __global__ void __launch_bounds__(kThreads) attn_dq_kernel(DqArgs a) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
   const int T = a.T, nkb = (T + kBlk - 1) / kBlk, nqb = (T + kFwdRows - 1) / kFwdRows;
   int j, bhi;
-  wg_map(nqb, j, bhi);
+  wg_map(nqb, a.G, j, bhi);
   const int qb = CAUSAL ? nqb - 1 - j : j;
   const int h = bhi % a.H, b = bhi / a.H;
   const int q0 = qb * kFwdRows, qw = q0 + w * 16 * kQT;
   const int64_t bh = static_cast<int64_t>(b) * a.H + h;
   const bf16_t* Qp = a.q + b * a.sq.b + h * a.sq.h;
-  const bf16_t* Kp = a.k + b * a.sk.b + h * a.sk.h;
-  const bf16_t* Vp = a.v + b * a.sv.b + h * a.sv.h;
+  const bf16_t* Kp = a.k + b * a.sk.b + (h / a.G) * a.sk.h;
+  const bf16_t* Vp = a.v + b * a.sv.b + (h / a.G) * a.sv.h;
   const bf16_t* dOp = a.dout + b * a.sdo.b + h * a.sdo.h;
   const uint8_t* KMp = a.md.km ? a.md.km + b * a.md.kms : nullptr;
 
@@ -724,32 +883,55 @@ static KeyMaskDrop make_md(const uint8_t* km, int64_t kms, uint32_t seed, const 
   return md;
 }
 
-// strides: 4 tensors (q, k, v, o) x (b, h, t) in elements; km: optional [B][kms] key mask
+// Workgroups per (batch, kv head) group of the grouped-query dK/dV kernel (the head split S).
+// The unsplit grid is nblk * B * Hkv workgroups, G times fewer than the MHA kernel's, each with G
+// times the work: multi-query attention at a modest batch leaves most of the 256 CUs idle.  Rule:
+// double S (up to G) while the grid stays below a target of 1024 workgroups (4 per CU), 2048 from
+// T = 4096 on.  Both figures are read off the sweep in profiles/attention_gqa_probe.txt (causal,
+// D = 128, H = 32, Hkv in {8, 4, 2, 1}, S in {1 .. G}): at T = 1024 the whole backward is fastest
+// with 1024 dK/dV workgroups for every Hkv (Hkv = 1: 1199 us unsplit, 408 at S = 8, 416 at S = 16;
+// Hkv = 8: 393 unsplit, 429 at S = 2), at T = 2048 1024 and 2048 workgroups are within 1-2%, and
+// at T = 4096 2048 workgroups win by 2-4% for every Hkv (Hkv = 1: 4806 us unsplit, 1331 at S = 8,
+// 1285 at S = 16, 1325 at S = 32).  Lengths between 2048 and 4096 and D = 64 were not swept.
+// DAMD_ATTN_GQA_SPLIT=<S> forces it (clamped to [1, G]; read per launch: the tests switch it).
+int damd_attn_gqa_split(int B, int Hkv, int G, int T) {
+  const char* e = getenv("DAMD_ATTN_GQA_SPLIT");
+  const int forced = e ? atoi(e) : 0;
+  if (forced >= 1) return forced < G ? forced : G;
+  const long wgs = static_cast<long>(B) * Hkv * ((T + kBlk - 1) / kBlk), target = T >= 4096 ? 2048 : 1024;
+  int S = 1;
+  while (2 * S <= G && wgs * S < target) S *= 2;
+  return S;
+}
+
+// strides: 4 tensors (q, k, v, o) x (b, h, t) in elements; km: optional [B][kms] key mask.
+// k, v have Hkv heads, H % Hkv == 0 (checked by the binding).
 void damd_attn_fwd_launch(const void* q, const void* k, const void* v, void* o, float* lse, const int64_t* strides,
-                          int B, int H, int T, int D, float scale, int causal, const uint8_t* km, int64_t kms,
-                          uint32_t seed, const int64_t* seedp, float drop_p, hipStream_t st) {
+                          int B, int H, int Hkv, int T, int D, float scale, int causal, const uint8_t* km,
+                          int64_t kms, uint32_t seed, const int64_t* seedp, float drop_p, hipStream_t st) {
   FwdArgs a;
   a.q = static_cast<const bf16_t*>(q); a.k = static_cast<const bf16_t*>(k); a.v = static_cast<const bf16_t*>(v);
   a.o = static_cast<bf16_t*>(o); a.lse = lse;
   a.sq = {strides[0], strides[1], strides[2]}; a.sk = {strides[3], strides[4], strides[5]};
   a.sv = {strides[6], strides[7], strides[8]}; a.so = {strides[9], strides[10], strides[11]};
-  a.H = H; a.T = T; a.scale_log2 = scale * kLog2e;
+  a.H = H; a.T = T; a.G = H / Hkv; a.scale_log2 = scale * kLog2e;
   a.md = make_md(km, kms, seed, seedp, drop_p);
   const int qt = attn_qt(false, B, H, T, D, causal), rows = fwd_rows(qt);
   dim3 grid(((T + rows - 1) / rows) * H * B);
   DAMD_ATTN_DISPATCH_QT(attn_fwd_kernel, qt, grid, a);
 }
 
-// strides: 8 tensors (q, k, v, o, dout, dk, dv, dq) x (b, h, t)
+// strides: 8 tensors (q, k, v, o, dout, dk, dv, dq) x (b, h, t).  k, v, dk, dv have Hkv heads.
+// Hkv < H: `split` is damd_attn_gqa_split(...) as the caller read it, and for split > 1 `part` holds
+// 2 * split * B * Hkv * T * D floats.
 void damd_attn_bwd_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
-                          const float* lse, float* delta, float* dq_acc, void* dq, void* dk, void* dv,
-                          const int64_t* s, int B, int H, int T, int D, float scale, int causal,
+                          const float* lse, float* delta, float* part, int split, void* dq, void* dk, void* dv,
+                          const int64_t* s, int B, int H, int Hkv, int T, int D, float scale, int causal,
                           const uint8_t* km, int64_t kms, uint32_t seed, const int64_t* seedp, float drop_p,
                           hipStream_t st) {
   const Strides sq{s[0], s[1], s[2]}, sk{s[3], s[4], s[5]}, sv{s[6], s[7], s[8]}, so{s[9], s[10], s[11]},
       sdo{s[12], s[13], s[14]}, sdk{s[15], s[16], s[17]}, sdv{s[18], s[19], s[20]}, sdq{s[21], s[22], s[23]};
   const int64_t rows = static_cast<int64_t>(B) * H * T;
-  (void)dq_acc;  // unused: dQ is produced by attn_dq_kernel without an fp32 accumulator
   {
     const int64_t threads = rows * (D / 8);
     const int blocks = static_cast<int>((threads + 255) / 256);
@@ -763,18 +945,31 @@ void damd_attn_bwd_launch(const void* q, const void* k, const void* v, const voi
   }
   BwdArgs a;
   a.q = static_cast<const bf16_t*>(q); a.k = static_cast<const bf16_t*>(k); a.v = static_cast<const bf16_t*>(v);
-  a.dout = static_cast<const bf16_t*>(dout); a.lse = lse; a.delta = delta; a.dq_acc = dq_acc;
+  a.dout = static_cast<const bf16_t*>(dout); a.lse = lse; a.delta = delta; a.dq_acc = nullptr;
   a.dk = static_cast<bf16_t*>(dk); a.dv = static_cast<bf16_t*>(dv);
   a.sq = sq; a.sk = sk; a.sv = sv; a.sdo = sdo; a.sdk = sdk; a.sdv = sdv;
   a.H = H; a.T = T; a.scale = scale; a.scale_log2 = scale * kLog2e;
+  a.G = H / Hkv; a.S = a.G > 1 ? split : 1; a.part = part;
   a.md = make_md(km, kms, seed, seedp, drop_p);
-  dim3 grid(((T + kBlk - 1) / kBlk) * H * B);
-  DAMD_ATTN_DISPATCH(attn_bwd_kernel, grid, a);
+  const int nblk = (T + kBlk - 1) / kBlk;
+  if (a.G == 1) {
+    dim3 grid(nblk * H * B);
+    DAMD_ATTN_DISPATCH(attn_bwd_kernel, grid, a);
+  } else {
+    dim3 grid(nblk * Hkv * B * a.S);
+    DAMD_ATTN_DISPATCH(attn_bwd_gqa_kernel, grid, a);
+    if (a.S > 1) {
+      const int64_t plane = static_cast<int64_t>(B) * Hkv * T * D;
+      DAMD_LAUNCH(attn_gqa_sum_kernel, dim3(static_cast<unsigned>((plane / 4 + 255) / 256)), dim3(256), 0, st, part,
+                  a.S, a.dk, sdk, a.dv, sdv, Hkv, T, D, plane);
+      DAMD_CHECK_LAUNCH();
+    }
+  }
   DqArgs d;
   d.q = a.q; d.k = a.k; d.v = a.v; d.dout = a.dout; d.lse = lse; d.delta = delta;
   d.dq = static_cast<bf16_t*>(dq);
   d.sq = sq; d.sk = sk; d.sv = sv; d.sdo = sdo; d.sdq = sdq;
-  d.H = H; d.T = T; d.scale = scale; d.scale_log2 = scale * kLog2e;
+  d.H = H; d.T = T; d.G = a.G; d.scale = scale; d.scale_log2 = scale * kLog2e;
   d.md = a.md;
   const int qt = attn_qt(true, B, H, T, D, causal), qrows = fwd_rows(qt);
   dim3 qgrid(((T + qrows - 1) / qrows) * H * B);

@@ -181,11 +181,13 @@ extern "C" int damd_stem_wgrad_blocks(int64_t, int);
 extern "C" void damd_stem_wgrad_launch(const void*, const void*, float*, void*, int, int64_t, int, int, hipStream_t);
 // launchers (attention.hip)
 extern "C" void damd_attn_fwd_launch(const void*, const void*, const void*, void*, float*, const int64_t*, int, int,
-                                     int, int, float, int, const uint8_t*, int64_t, uint32_t, const int64_t*, float,
-                                     hipStream_t);
+                                     int, int, int, float, int, const uint8_t*, int64_t, uint32_t, const int64_t*,
+                                     float, hipStream_t);
+extern "C" int damd_attn_gqa_split(int, int, int, int);
 extern "C" void damd_attn_bwd_launch(const void*, const void*, const void*, const void*, const void*, const float*,
-                                     float*, float*, void*, void*, void*, const int64_t*, int, int, int, int, float,
-                                     int, const uint8_t*, int64_t, uint32_t, const int64_t*, float, hipStream_t);
+                                     float*, float*, int, void*, void*, void*, const int64_t*, int, int, int, int, int,
+                                     float, int, const uint8_t*, int64_t, uint32_t, const int64_t*, float,
+                                     hipStream_t);
 // launchers (fused.hip)
 extern "C" void damd_lm_ce_fwd_launch(const void*, const int64_t*, int64_t, int, int, int, int64_t, float*, float*,
                                       hipStream_t);
@@ -1471,6 +1473,16 @@ void check_attn(const at::Tensor& t, const at::Tensor& ref, const char* what) {
   TORCH_CHECK(t.sizes() == ref.sizes(), what, " shape mismatch");
 }
 
+// k (and v, dk, dv through check_attn(., k)) against q: [B, Hkv, T, D] with H % Hkv == 0 --
+// grouped-query attention when Hkv < H.
+void check_attn_kv(const at::Tensor& k, const at::Tensor& q) {
+  TORCH_CHECK(attn_supported(k), "k: unsupported layout (need bf16 [B,Hkv,T,D], D in {64,128}, contiguous D, "
+              "16-byte aligned strides)");
+  TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2) && k.size(3) == q.size(3) && k.size(1) > 0 &&
+                  q.size(1) % k.size(1) == 0,
+              "k shape mismatch: need [B, Hkv, T, D] with q's B, T, D and Hkv dividing q's ", q.size(1), " heads");
+}
+
 void push_strides(std::vector<int64_t>& s, const at::Tensor& t) {
   s.push_back(t.stride(0));
   s.push_back(t.stride(1));
@@ -1496,8 +1508,8 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const
                                  double scale, const c10::optional<at::Tensor>& kmask, double drop_p, int64_t seed,
                                  const c10::optional<at::Tensor>& seed_t) {
   check_attn(q, q, "q");
-  check_attn(k, q, "k");
-  check_attn(v, q, "v");
+  check_attn_kv(k, q);
+  check_attn(v, k, "v");
   TORCH_CHECK(drop_p >= 0.0 && drop_p < 1.0, "dropout probability must be in [0, 1)");
   int64_t kms = 0;
   const uint8_t* km = check_kmask(kmask, q, &kms);
@@ -1512,9 +1524,9 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const
   push_strides(s, o);
   if (B * H * T > 0)
     damd_attn_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), s.data(),
-                         static_cast<int>(B), static_cast<int>(H), static_cast<int>(T), static_cast<int>(D),
-                         static_cast<float>(scale), causal ? 1 : 0, km, kms, static_cast<uint32_t>(seed),
-                         seed_ptr(seed_t, q), static_cast<float>(drop_p), cur_stream());
+                         static_cast<int>(B), static_cast<int>(H), static_cast<int>(k.size(1)), static_cast<int>(T),
+                         static_cast<int>(D), static_cast<float>(scale), causal ? 1 : 0, km, kms,
+                         static_cast<uint32_t>(seed), seed_ptr(seed_t, q), static_cast<float>(drop_p), cur_stream());
   return {o, lse};
 }
 
@@ -1523,29 +1535,37 @@ void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, 
               double scale, const c10::optional<at::Tensor>& kmask, double drop_p, int64_t seed,
               const c10::optional<at::Tensor>& seed_t) {
   check_attn(q, q, "q");
-  check_attn(k, q, "k");
-  check_attn(v, q, "v");
+  check_attn_kv(k, q);
+  check_attn(v, k, "v");
   check_attn(o, q, "o");
   check_attn(dout, q, "dout");
   check_attn(dq, q, "dq");
-  check_attn(dk, q, "dk");
-  check_attn(dv, q, "dv");
-  const int64_t B = q.size(0), H = q.size(1), T = q.size(2), D = q.size(3);
+  check_attn(dk, k, "dk");
+  check_attn(dv, k, "dv");
+  const int64_t B = q.size(0), H = q.size(1), Hkv = k.size(1), T = q.size(2), D = q.size(3);
   TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == B * H * T, "lse [B,H,T] f32");
   auto delta = at::empty({B, H, T}, lse.options());
   int64_t kms = 0;
   const uint8_t* km = check_kmask(kmask, q, &kms);
+  // grouped-query dK/dV with the group's heads split over `split` workgroups: fp32 partials
+  int split = 1;
+  at::Tensor part;
+  if (Hkv < H && B * H * T > 0) {
+    split = damd_attn_gqa_split(static_cast<int>(B), static_cast<int>(Hkv), static_cast<int>(H / Hkv),
+                                static_cast<int>(T));
+    if (split > 1) part = at::empty({2, split, B, Hkv, T, D}, lse.options());
+  }
 
   std::vector<int64_t> s;
   const at::Tensor* order[] = {&q, &k, &v, &o, &dout, &dk, &dv, &dq};
   for (const at::Tensor* t : order) push_strides(s, *t);
   if (B * H * T > 0)
     damd_attn_bwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
-                         lse.data_ptr<float>(), delta.data_ptr<float>(), nullptr, dq.data_ptr(),
-                         dk.data_ptr(), dv.data_ptr(), s.data(), static_cast<int>(B), static_cast<int>(H),
-                         static_cast<int>(T), static_cast<int>(D), static_cast<float>(scale), causal ? 1 : 0,
-                         km, kms, static_cast<uint32_t>(seed), seed_ptr(seed_t, q), static_cast<float>(drop_p),
-                         cur_stream());
+                         lse.data_ptr<float>(), delta.data_ptr<float>(),
+                         part.defined() ? part.data_ptr<float>() : nullptr, split, dq.data_ptr(), dk.data_ptr(),
+                         dv.data_ptr(), s.data(), static_cast<int>(B), static_cast<int>(H), static_cast<int>(Hkv),
+                         static_cast<int>(T), static_cast<int>(D), static_cast<float>(scale), causal ? 1 : 0, km, kms,
+                         static_cast<uint32_t>(seed), seed_ptr(seed_t, q), static_cast<float>(drop_p), cur_stream());
 }
 
 // ---------------------------------------------------------------- fused LM loss / bias grad

@@ -4,7 +4,9 @@ GPU (bf16, head dim 64 or 128): the hand-written MFMA flash-attention kernels in
 ``csrc/attention.hip`` (online softmax, no [T, T] matrix in HBM; backward recomputes P from the
 saved log-sum-exp), with an optional key-padding mask (BERT batches) and in-kernel dropout on the
 attention probabilities (a counter-based keep decision recomputed by the backward -- no mask is
-stored).  ``qkv_attention`` takes the packed ``[B, T, 3, H, D]`` projection output directly and
+stored).  Grouped-query / multi-query attention: ``k`` / ``v`` with ``Hkv < H`` heads (``H % Hkv ==
+0``) go to the kernels as they are -- no repeated K/V, and dK / dV come back with ``Hkv`` heads,
+summed over each group inside the dK/dV kernel.  ``qkv_attention`` (MHA only) takes the packed ``[B, T, 3, H, D]`` projection output directly and
 writes dQ/dK/dV into ONE gradient buffer of that shape, so the backward needs no concatenation of
 three gradients.
 
@@ -104,8 +106,13 @@ class _FlashAttnFn(torch.autograd.Function):
         if not _ext().attn_supported(do):
             do = do.transpose(1, 2).contiguous().transpose(1, 2)
         B, H, T, D = q.shape
-        g = torch.empty(3, B, T, H, D, dtype=q.dtype, device=q.device).permute(0, 1, 3, 2, 4)
-        dq, dk, dv = g[0], g[1], g[2]
+        Hkv = k.shape[1]
+        if Hkv == H:
+            g = torch.empty(3, B, T, H, D, dtype=q.dtype, device=q.device).permute(0, 1, 3, 2, 4)
+            dq, dk, dv = g[0], g[1], g[2]
+        else:  # grouped-query: the kernel sums each group's heads, dK / dV have Hkv heads
+            dq = torch.empty(B, T, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
+            dk, dv = torch.empty(2, B, T, Hkv, D, dtype=q.dtype, device=q.device).permute(0, 1, 3, 2, 4).unbind(0)
         _ext().attn_bwd(do, q, k, v, o, lse, dq, dk, dv, ctx.causal, ctx.scale, ctx.km, ctx.dropout_p, ctx.seed[0],
                         ctx.seed[1])
         return dq, dk, dv, None, None, None, None, None
@@ -139,8 +146,10 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: b
                     scale: Optional[float] = None, key_padding: Optional[torch.Tensor] = None,
                     dropout_p: float = 0.0) -> torch.Tensor:
     """Fused attention for ``[B, H, T, D]`` bf16 tensors on the GPU (raises if unsupported).
-    ``key_padding``: a ``key_mask`` tensor (or a ``[B, T]`` validity mask); ``dropout_p``:
-    attention-probability dropout (in-kernel)."""
+    ``k`` / ``v`` may have ``Hkv`` heads with ``H % Hkv == 0`` (grouped-query / multi-query
+    attention: query head ``h`` reads K/V head ``h // (H // Hkv)``; their gradients have ``Hkv``
+    heads).  ``key_padding``: a ``key_mask`` tensor (or a ``[B, T]`` validity mask);
+    ``dropout_p``: attention-probability dropout (in-kernel)."""
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else scale
     if not _supported(q, k, v):
         raise ValueError("flash_attention needs bf16 GPU tensors [B,H,T,D] with D in {64,128} and a contiguous D")
@@ -151,13 +160,15 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: b
 
 
 def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dropout_p: float = 0.0) -> torch.Tensor:
-    """``softmax(q k^T / sqrt(d) + causal_mask) v`` for ``[B, H, T, D]`` tensors."""
+    """``softmax(q k^T / sqrt(d) + causal_mask) v`` for ``[B, H, T, D]`` tensors; ``k`` / ``v`` may be
+    ``[B, Hkv, T, D]`` with ``H % Hkv == 0`` (grouped-query attention)."""
     if q.is_cuda and _supported(q, k, v):
         return _FlashAttnFn.apply(q, k, v, True, 1.0 / math.sqrt(q.shape[-1]), None, float(dropout_p),
                                   dropout_seed(dropout_p, q.device))
     if q.is_cuda:
         _configure()
-    return F.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p, is_causal=True)
+    return F.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p, is_causal=True,
+                                          enable_gqa=k.shape[1] != q.shape[1])
 
 
 def qkv_attention(qkv: torch.Tensor, causal: bool = True, dropout_p: float = 0.0,

@@ -1,11 +1,14 @@
-"""Route a HuggingFace encoder's hot ops through determined_amd's MI355X kernels.
+"""Route a HuggingFace model's hot ops through determined_amd's MI355X kernels.
 
-``accelerate(model)`` (BERT / RoBERTa-style encoders, ``transformers`` 5.x):
+``accelerate(model)`` (BERT / RoBERTa-style encoders and Llama / Mistral / Qwen2-style decoders,
+``transformers`` 5.x):
 
-* attention -> ``csrc/attention.hip`` flash attention (non-causal, key-padding mask, in-kernel
+* attention -> ``csrc/attention.hip`` flash attention (causal or not, key-padding mask, in-kernel
   attention-probability dropout), registered as the ``"damd"`` attention implementation through
   ``AttentionInterface`` together with a mask function that hands the kernel its uint8 key mask
-  (built once per forward, ``None`` for unpadded batches);
+  (built once per forward, ``None`` for unpadded batches).  Grouped-query / multi-query decoders
+  pass their un-repeated ``[B, Hkv, T, D]`` key / value straight to the grouped-query kernels;
+* ``LlamaRMSNorm`` / ``MistralRMSNorm`` / ``Qwen2RMSNorm`` -> ``FusedRMSNorm`` (``csrc/norm.hip``);
 * ``BertSelfOutput`` / ``BertOutput`` (dense -> dropout -> LayerNorm(. + residual)) -> the dense GEMM
   followed by ONE ``csrc/norm.hip`` kernel doing residual add + dropout + LayerNorm (its backward
   emits both gradients in one pass);
@@ -27,7 +30,7 @@ import torch
 from torch import nn
 
 from determined_amd.ops.attention import _supported, flash_attention, key_mask
-from determined_amd.ops.norm import FusedLayerNorm, residual_dropout_layer_norm
+from determined_amd.ops.norm import FusedLayerNorm, FusedRMSNorm, residual_dropout_layer_norm
 
 NAME = "damd"
 _MASK_SHORTCUT = os.environ.get("DAMD_MASK_SHORTCUT", "0") == "1"
@@ -56,7 +59,8 @@ def _damd_attention(module: nn.Module, query: torch.Tensor, key: torch.Tensor, v
     causal = bool(getattr(module, "is_causal", False) if is_causal is None else is_causal)
     same_len = query.shape[2] == key.shape[2]
     kernel_mask = attention_mask is None or (attention_mask.dtype == torch.uint8 and attention_mask.dim() == 2)
-    if same_len and kernel_mask:
+    # grouped-query models (Llama, Mistral, Qwen, ...) hand over the un-repeated [B, Hkv, T, D] key / value
+    if same_len and kernel_mask and query.shape[1] % key.shape[1] == 0:
         km = attention_mask
         q, k, v = (t if t.stride(-1) == 1 else t.contiguous() for t in (query, key, value))
         if _supported(q, k, v):
@@ -67,9 +71,13 @@ def _damd_attention(module: nn.Module, query: torch.Tensor, key: torch.Tensor, v
     mask = attention_mask
     if mask is not None and mask.dtype == torch.uint8 and mask.dim() == 2:
         mask = mask[:, None, None, : key.shape[2]].bool()
-    o = torch.nn.functional.scaled_dot_product_attention(query, key, value, attn_mask=mask,
+        if causal:  # a decoder batch with padding: SDPA takes one mask, so fold the causal one in
+            tq, tk = query.shape[2], key.shape[2]
+            mask = mask & torch.ones(tq, tk, dtype=torch.bool, device=mask.device).tril(tk - tq)
+    o =torch.nn.functional.scaled_dot_product_attention(query, key, value, attn_mask=mask,
                                                          dropout_p=dropout if module.training else 0.0,
-                                                         is_causal=causal and mask is None, scale=scaling)
+                                                         is_causal=causal and mask is None, scale=scaling,
+                                                         enable_gqa=key.shape[1] != query.shape[1])
     return o.transpose(1, 2).contiguous(), None
 
 
@@ -133,6 +141,18 @@ def _to_fused(ln: nn.LayerNorm) -> FusedLayerNorm:
     return f
 
 
+# ``weight * x / rms(x)`` norms, by class name: not ``*RMSNorm`` -- Gemma's scales by ``1 + weight``
+_RMS_NORMS = ("LlamaRMSNorm", "MistralRMSNorm", "Qwen2RMSNorm")
+
+
+def _to_fused_rms(norm: nn.Module) -> FusedRMSNorm:
+    f = FusedRMSNorm(norm.weight.shape[0], eps=norm.variance_epsilon, device=norm.weight.device,
+                     dtype=norm.weight.dtype)
+    with torch.no_grad():
+        f.weight.copy_(norm.weight)
+    return f
+
+
 def accelerate(model: nn.Module, sparse_mlm_head: bool = False) -> nn.Module:
     """Swap in the fused kernels (in place; returns ``model``).  Parameters keep their names, so
     checkpoints stay loadable by the stock modules.
@@ -157,6 +177,8 @@ def accelerate(model: nn.Module, sparse_mlm_head: bool = False) -> nn.Module:
         for child_name, child in list(mod.named_children()):
             if isinstance(child, nn.LayerNorm) and len(child.normalized_shape) == 1:
                 setattr(mod, child_name, _to_fused(child))
+            elif type(child).__name__ in _RMS_NORMS:
+                setattr(mod, child_name, _to_fused_rms(child))
     from determined_amd.ops.fused import FusedLinear
 
     for mod in model.modules():  # Linear + GELU (BERT-style *Intermediate): one GELU pass, gelu' fused with the bias gradient
