@@ -1,5 +1,5 @@
 // Flash attention (forward + backward) for gfx950 / MI355X: bf16 in/out, fp32 accumulate,
-// online softmax, optional causal mask, head dim D in {64, 128}.
+// online softmax, full / causal / band masks, head dim D in {64, 128}.
 //
 // MFMA: v_mfma_f32_16x16x32_bf16 (a 64-wide wave computes a 16x16 tile, K = 32).
 //   A operand: lane l holds A[row l&15][k 8(l>>4)+j], B operand: B[k 8(l>>4)+j][col l&15],
@@ -32,6 +32,25 @@
 // Grouped-query attention (K / V with Hkv heads, G = H / Hkv query heads per K/V head): the
 //   forward and dQ kernels index K / V by h / G and keep one group's workgroups on one XCD
 //   (wg_map); dK/dV is attn_bwd_gqa_kernel, which sums the group's heads in its accumulators.
+//
+// Band mode (sliding windows, packed documents; the third mask mode next to full and causal):
+//   query q attends the contiguous keys [klo[q], khi[q]), both bounds non-decreasing in q, so the
+//   queries of key k are contiguous too, [qlo[k], qhi[k]) -- four int32 arrays per batch row (or one
+//   shared row), padded to a multiple of 128 entries with empty ranges so tile-granular loads need
+//   no bounds branch.  The query-major kernels (forward, dQ) visit only the key tiles between
+//   klo[first row] / 64 and ceil(khi[last valid row] / 64) -- monotone bounds make these the minimum
+//   and maximum -- with the K/V prefetch starting at the first visited tile; the key-major kernels
+//   (dK/dV, grouped-query dK/dV: one range for every head of the group) visit only the query blocks
+//   between qlo[first key] / 64 and ceil(qhi[last valid key] / 64): O(T * W) instead of O(T^2).
+//   The element mask is two integer compares against the lane's own (lo, hi) registers, taken only
+//   in tiles that are not interior to every row's (key's) range; at D = 64 the forward's interior
+//   tiles run the maskless body between masked leading and trailing edge tiles.  Workgroups run in
+//   natural order (band work per block is roughly even).  The key mask and dropout compose as in
+//   causal mode: the dropout counter is (seed, b*H + h, q, k) whatever the mask mode.
+//   Registers at D = 64 (band instantiations, no dropout / dropout; waves per SIMD): forward QT = 1
+//   104 / 114 VGPRs (4), QT = 2 156 / 164 (3) -- the same occupancy as causal (three loop copies of
+//   the tile body; choosing the body per tile inside ONE loop took 200 VGPRs, 2 waves); dQ QT = 1
+//   118 / 120 (4), QT = 2 196 / 200 (2); dK/dV 134 / 136 (3), grouped-query dK/dV 142 / 148 (3).
 //
 // Strides are in elements for (batch, head, token); the head dimension must be contiguous.
 //
@@ -95,12 +114,24 @@ __device__ __forceinline__ uint32_t md_seed(const KeyMaskDrop& md) {
   return md.seedp != nullptr ? static_cast<uint32_t>(*md.seedp) : md.seed;
 }
 
+// Mask mode of the four attention kernels (a template argument).  Band: query q attends the keys
+// [klo[q], khi[q]) and key k is attended by the queries [qlo[k], qhi[k]) -- two descriptions of one
+// staircase, both bounds non-decreasing (sliding windows, packed documents).
+constexpr int kFull = 0, kCausal = 1, kBand = 2;
+
+struct Band {
+  const int32_t* klo; const int32_t* khi;  // [b][query], rows padded to a multiple of 128 with empty ranges
+  const int32_t* qlo; const int32_t* qhi;  // [b][key], likewise
+  int64_t bs;                              // row stride (0: one row for every batch element)
+};
+
 struct FwdArgs {
   const bf16_t* q; const bf16_t* k; const bf16_t* v; bf16_t* o; float* lse;
   Strides sq, sk, sv, so;
   int H, T, G;  // G = H / Hkv query heads per K/V head
   float scale_log2;  // softmax scale * log2(e)
   KeyMaskDrop md;
+  Band band;
 };
 
 struct BwdArgs {
@@ -112,7 +143,44 @@ struct BwdArgs {
   float* part;       // S > 1: fp32 partials [2 (dk, dv)][S][B * Hkv][T][D]
   float scale, scale_log2;
   KeyMaskDrop md;
+  Band band;
 };
+
+// Key-tile range of a query-major workgroup (forward, dQ) in band mode, rows [q0, q0 + rows): the
+// tiles [begin, end) hold every attended key -- the bounds are non-decreasing, so the first row has
+// the lowest klo and the last valid row the highest khi -- and the tiles [full_lo, full_hi) lie
+// inside every row's range (no masking needed).  Clamped to the tiles that exist, whatever the
+// arrays hold.
+struct KeyTiles {
+  int begin, end, full_lo, full_hi;
+};
+__device__ __forceinline__ KeyTiles band_key_tiles(const int32_t* klo, const int32_t* khi, int q0, int rows, int T) {
+  const int ql = min(q0 + rows, T) - 1, nkb = (T + kBlk - 1) / kBlk;
+  const int lo_first = max(klo[q0], 0), lo_last = max(klo[ql], 0);
+  const int hi_first = min(khi[q0], T), hi_last = min(khi[ql], T);
+  KeyTiles t;
+  t.begin = min(lo_first / kBlk, nkb);
+  t.end = max(t.begin, (hi_last + kBlk - 1) / kBlk);
+  t.full_lo = (lo_last + kBlk - 1) / kBlk;
+  t.full_hi = hi_first / kBlk;
+  return t;
+}
+
+// The same for a key-major workgroup (dK/dV) with the keys [k0, k0 + 64): the 64-row query blocks
+// [begin, end) hold every query that attends one of its keys, and the queries [in_lo, in_hi)
+// attend all of them.
+struct QueryBlocks {
+  int begin, end, in_lo, in_hi;
+};
+__device__ __forceinline__ QueryBlocks band_query_blocks(const int32_t* qlo, const int32_t* qhi, int k0, int T) {
+  const int kl = min(k0 + kBlk, T) - 1, nblk = (T + kBlk - 1) / kBlk;
+  QueryBlocks t;
+  t.begin = min(max(qlo[k0], 0) / kBlk, nblk);
+  t.end = max(t.begin, (min(qhi[kl], T) + kBlk - 1) / kBlk);
+  t.in_lo = max(qlo[kl], 0);
+  t.in_hi = min(qhi[k0], T);
+  return t;
+}
 
 // dropout decision for (b*H + h, query, key): murmur3-style finalizer of the mixed counters
 __device__ __forceinline__ bool drop_keep(uint32_t seed, uint32_t thresh, uint32_t bh, uint32_t q, uint32_t k) {
@@ -238,8 +306,9 @@ __device__ __forceinline__ void wg_map(int nblk, int G, int& j, int& bh) {
 // ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
-template <int D, int kQT, bool CAUSAL, bool DROP>
+template <int D, int kQT, int MODE, bool DROP>
 __global__ void __launch_bounds__(kThreads) attn_fwd_kernel(FwdArgs a) {
+  constexpr bool CAUSAL = MODE == kCausal, BAND = MODE == kBand;
   constexpr int kFwdRows = fwd_rows(kQT);
   constexpr int KP = kLdsStride(D);
   __shared__ __attribute__((aligned(16))) bf16_t Ks[kBlk * KP];
@@ -258,9 +327,14 @@ __global__ void __launch_bounds__(kThreads) attn_fwd_kernel(FwdArgs a) {
   const uint32_t bh32 = static_cast<uint32_t>(b * a.H + h);
 
   s8 qf[kQT][D / 32];
+  int klo[kQT], khi[kQT];  // band: the lane's key range, one per 16-row tile
 #pragma unroll
   for (int qt = 0; qt < kQT; ++qt) {
     const int q = qw + qt * 16 + c;
+    if constexpr (BAND) {  // q < padded row length
+      klo[qt] = a.band.klo[b * a.band.bs + q];
+      khi[qt] = min(a.band.khi[b * a.band.bs + q], T);
+    }
 #pragma unroll
     for (int ds = 0; ds < D / 32; ++ds) {
       s8 x = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -278,10 +352,12 @@ __global__ void __launch_bounds__(kThreads) attn_fwd_kernel(FwdArgs a) {
     for (int dt = 0; dt < D / 16; ++dt) oacc[qt][dt] = f4{0.f, 0.f, 0.f, 0.f};
   }
 
-  const int kb_end = CAUSAL ? min(nkb, (q0 + kFwdRows - 1) / kBlk + 1) : nkb;
+  KeyTiles bt = {0, 0, 0, 0};
+  if constexpr (BAND) bt = band_key_tiles(a.band.klo + b * a.band.bs, a.band.khi + b * a.band.bs, q0, kFwdRows, T);
+  const int kb_end = BAND ? bt.end : CAUSAL ? min(nkb, (q0 + kFwdRows - 1) / kBlk + 1) : nkb;
   Stage<D, kBlk> ks, vs;
-  ks.load(Kp, a.sk.t, 0, T);
-  vs.load(Vp, a.sv.t, 0, T);
+  ks.load(Kp, a.sk.t, bt.begin * kBlk, T);
+  vs.load(Vp, a.sv.t, bt.begin * kBlk, T);
   // Leading tiles that no row of the workgroup masks (all keys < T and <= q0) run a body
   // compiled without any masking code; only the <= 2 diagonal / ragged tiles carry the selects.
   // (D = 128: a single masked body -- the unmasked copy pushes it to 256 VGPRs, 1 wave / SIMD)
@@ -320,8 +396,11 @@ __global__ void __launch_bounds__(kThreads) attn_fwd_kernel(FwdArgs a) {
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-          for (int r = 0; r < 4; ++r)
-            s[qt][nt][r] = (k0 + nt * 16 + 4 * g + r > kmax) ? -INFINITY : s[qt][nt][r];
+          for (int r = 0; r < 4; ++r) {
+            const int key = k0 + nt * 16 + 4 * g + r;
+            const bool out = BAND ? (key < klo[qt] || key >= khi[qt]) : key > kmax;
+            s[qt][nt][r] = out ? -INFINITY : s[qt][nt][r];
+          }
         if (KMp) {  // padded keys (row padded to a multiple of 64: the word loads stay in bounds)
 #pragma unroll
           for (int nt = 0; nt < 4; ++nt) {
@@ -371,9 +450,22 @@ __global__ void __launch_bounds__(kThreads) attn_fwd_kernel(FwdArgs a) {
       }
     }
   };
-  int kb = 0;
-  for (; kb < kb_full; ++kb) tile(kb, std::false_type{});
-  for (; kb < kb_end; ++kb) tile(kb, std::true_type{});
+  if constexpr (BAND) {
+    // band: masked edge tiles on both sides of the interior ones; at D = 64 without a key mask
+    // the interior tiles take the maskless body
+    int kb = bt.begin;
+    if constexpr (D == 64) {
+      if (!KMp) {
+        for (const int e = min(bt.full_lo, kb_end); kb < e; ++kb) tile(kb, std::true_type{});
+        for (const int e = min(bt.full_hi, kb_end); kb < e; ++kb) tile(kb, std::false_type{});
+      }
+    }
+    for (; kb < kb_end; ++kb) tile(kb, std::true_type{});
+  } else {
+    int kb = 0;
+    for (; kb < kb_full; ++kb) tile(kb, std::false_type{});
+    for (; kb < kb_end; ++kb) tile(kb, std::true_type{});
+  }
 #pragma unroll
   for (int qt = 0; qt < kQT; ++qt) {
     const float lt = rows_sum(l[qt]);
@@ -422,16 +514,20 @@ __global__ void __launch_bounds__(256) attn_delta_kernel(const bf16_t* __restric
 
 // One 64-query block of the dK/dV pass for a wave's 16 keys: the block's Q / dO tiles and its
 // lse (x log2 e) / delta rows are staged in LDS, the K / V fragments of the keys stay in registers,
-// dk / dv accumulate.  bh = b*H + (query head): the dropout counter.
-template <int D, bool CAUSAL, bool DROP>
+// dk / dv accumulate.  bh = b*H + (query head): the dropout counter.  Band mode: [qlo, qhi) is the
+// query range of the lane's key, and the block [q0, q0 + 64) is interior when it lies inside the
+// range of every key of the workgroup (kr: see band_query_blocks).
+template <int D, int MODE, bool DROP>
 __device__ __forceinline__ void bwd_block(const BwdArgs& a, const bf16_t* Qs, const bf16_t* dOs, const float* lse2,
                                           const float* dl, const s8 (&kf)[D / 32], const s8 (&vf)[D / 32],
                                           f4 (&dk)[D / 16], f4 (&dv)[D / 16], uint32_t bh, int q0, int k0, int mykey,
-                                          bool kvalid, bool has_km) {
+                                          bool kvalid, bool has_km, int qlo, int qhi, const QueryBlocks& kr) {
+  constexpr bool CAUSAL = MODE == kCausal, BAND = MODE == kBand;
   constexpr int RP = kLdsStride(D);
   const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
   const int T = a.T;
-  const bool need_mask = (k0 + kBlk > T) || (CAUSAL && q0 < k0 + kBlk) || has_km;
+  const bool need_mask = (k0 + kBlk > T) || (CAUSAL && q0 < k0 + kBlk) || has_km ||
+                         (BAND && (q0 < kr.in_lo || q0 + kBlk > kr.in_hi));
   // two halves of 32 queries: S / dP -> P / dS of one half feed its dV / dK MFMAs right away
   // (half the live P / dS registers: <= 128 VGPRs at D = 64, 4 waves per SIMD)
 #pragma unroll
@@ -452,7 +548,8 @@ __device__ __forceinline__ void bwd_block(const BwdArgs& a, const bf16_t* Qs, co
       for (int r = 0; r < 4; ++r) {
         const int ql = qt * 16 + 4 * g + r;
         float p = ex2(fmaf(sacc[r], a.scale_log2, -lse2[ql]));
-        if (need_mask) p = (!kvalid || (CAUSAL && mykey > q0 + ql)) ? 0.f : p;
+        if (need_mask)
+          p = (!kvalid || (CAUSAL && mykey > q0 + ql) || (BAND && (q0 + ql < qlo || q0 + ql >= qhi))) ? 0.f : p;
         if constexpr (DROP) {
           const bool keep = drop_keep(md_seed(a.md), a.md.thresh, bh, q0 + ql, mykey);
           P[hq][r] = keep ? p * a.md.inv_keep : 0.f;  // dV uses the dropped, rescaled probabilities
@@ -474,8 +571,9 @@ __device__ __forceinline__ void bwd_block(const BwdArgs& a, const bf16_t* Qs, co
   }
 }
 
-template <int D, bool CAUSAL, bool DROP>
+template <int D, int MODE, bool DROP>
 __global__ void __launch_bounds__(kThreads) attn_bwd_kernel(BwdArgs a) {
+  constexpr bool CAUSAL = MODE == kCausal, BAND = MODE == kBand;
   constexpr int RP = kLdsStride(D);
   __shared__ __attribute__((aligned(16))) bf16_t Qs[kBlk * RP];
   __shared__ __attribute__((aligned(16))) bf16_t dOs[kBlk * RP];
@@ -511,11 +609,20 @@ __global__ void __launch_bounds__(kThreads) attn_bwd_kernel(BwdArgs a) {
 #pragma unroll
   for (int dt = 0; dt < D / 16; ++dt) dk[dt] = dv[dt] = f4{0.f, 0.f, 0.f, 0.f};
 
-  const int qb0 = CAUSAL ? kb : 0;
+  // band: the lane's query range (mykey < padded row length) and the workgroup's query blocks
+  QueryBlocks kr = {0, 0, 0, 0};
+  int qlo = 0, qhi = 0;
+  if constexpr (BAND) {
+    const int64_t row = b * a.band.bs;
+    kr = band_query_blocks(a.band.qlo + row, a.band.qhi + row, k0, T);
+    qlo = a.band.qlo[row + mykey];
+    qhi = a.band.qhi[row + mykey];
+  }
+  const int qb0 = BAND ? kr.begin : CAUSAL ? kb : 0, qb_end = BAND ? kr.end : nblk;
   Stage<D, kBlk> qst, ost;
   qst.load(Qp, a.sq.t, qb0 * kBlk, T);
   ost.load(dOp, a.sdo.t, qb0 * kBlk, T);
-  for (int qb = qb0; qb < nblk; ++qb) {
+  for (int qb = qb0; qb < qb_end; ++qb) {
     const int q0 = qb * kBlk;
     __syncthreads();
     qst.store(Qs);
@@ -526,13 +633,13 @@ __global__ void __launch_bounds__(kThreads) attn_bwd_kernel(BwdArgs a) {
       dl[threadIdx.x] = q < T ? a.delta[bh * T + q] : 0.f;
     }
     __syncthreads();
-    if (qb + 1 < nblk) {
+    if (qb + 1 < qb_end) {
       qst.load(Qp, a.sq.t, q0 + kBlk, T);
       ost.load(dOp, a.sdo.t, q0 + kBlk, T);
     }
 
-    bwd_block<D, CAUSAL, DROP>(a, Qs, dOs, lse2, dl, kf, vf, dk, dv, static_cast<uint32_t>(bh), q0, k0, mykey, kvalid,
-                               KMp != nullptr);
+    bwd_block<D, MODE, DROP>(a, Qs, dOs, lse2, dl, kf, vf, dk, dv, static_cast<uint32_t>(bh), q0, k0, mykey, kvalid,
+                             KMp != nullptr, qlo, qhi, kr);
   }
   if (mykey < T) {
     bf16_t* dKp = a.dk + b * a.sdk.b + h * a.sdk.h + static_cast<int64_t>(mykey) * a.sdk.t;
@@ -562,8 +669,9 @@ __global__ void __launch_bounds__(kThreads) attn_bwd_kernel(BwdArgs a) {
 // Head split (a.S > 1, small grids): workgroup part s of S takes the heads [s*G/S, (s+1)*G/S) of
 // the group (uneven when S does not divide G; S <= G, so no part is empty) and writes fp32
 // partials a.part[dk|dv][s][b*Hkv + hkv][key][D]; attn_gqa_sum_kernel adds them in part order.
-template <int D, bool CAUSAL, bool DROP>
+template <int D, int MODE, bool DROP>
 __global__ void __launch_bounds__(kThreads) attn_bwd_gqa_kernel(BwdArgs a) {
+  constexpr bool CAUSAL = MODE == kCausal, BAND = MODE == kBand;
   constexpr int RP = kLdsStride(D);
   __shared__ __attribute__((aligned(16))) bf16_t Qs[kBlk * RP];
   __shared__ __attribute__((aligned(16))) bf16_t dOs[kBlk * RP];
@@ -600,12 +708,23 @@ __global__ void __launch_bounds__(kThreads) attn_bwd_gqa_kernel(BwdArgs a) {
 #pragma unroll
   for (int dt = 0; dt < D / 16; ++dt) dk[dt] = dv[dt] = f4{0.f, 0.f, 0.f, 0.f};
 
-  const int qb0 = CAUSAL ? kb : 0;
-  int h = hkv * a.G + hg0;  // query head of the iteration
+  // band: one query-block range for every head of the group
+  QueryBlocks kr = {0, 0, 0, 0};
+  int qlo = 0, qhi = 0;
+  if constexpr (BAND) {
+    const int64_t row = b * a.band.bs;
+    kr = band_query_blocks(a.band.qlo + row, a.band.qhi + row, k0, T);
+    qlo = a.band.qlo[row + mykey];
+    qhi = a.band.qhi[row + mykey];
+  }
+  const int qb0 = BAND ? kr.begin : CAUSAL ? kb : 0, qb_end = BAND ? kr.end : nblk;
   const int h_end = hkv * a.G + hg1;
+  int h = BAND && qb0 >= qb_end ? h_end : hkv * a.G + hg0;  // query head of the iteration (band: no block, no iteration)
   Stage<D, kBlk> qst, ost;
-  qst.load(Qb + h * a.sq.h, a.sq.t, qb0 * kBlk, T);
-  ost.load(dOb + h * a.sdo.h, a.sdo.t, qb0 * kBlk, T);
+  if (!BAND || h < h_end) {
+    qst.load(Qb + h * a.sq.h, a.sq.t, qb0 * kBlk, T);
+    ost.load(dOb + h * a.sdo.h, a.sdo.t, qb0 * kBlk, T);
+  }
   for (int qb = qb0; h < h_end;) {
     const int q0 = qb * kBlk;
     const int64_t bh = static_cast<int64_t>(b) * a.H + h;
@@ -619,14 +738,14 @@ __global__ void __launch_bounds__(kThreads) attn_bwd_gqa_kernel(BwdArgs a) {
     }
     __syncthreads();
     // next iteration: the following query block, or the first block of the next head
-    const bool last = qb + 1 == nblk;
+    const bool last = qb + 1 == qb_end;
     const int nh = last ? h + 1 : h, nqb = last ? qb0 : qb + 1;
     if (nh < h_end) {
       qst.load(Qb + nh * a.sq.h, a.sq.t, nqb * kBlk, T);
       ost.load(dOb + nh * a.sdo.h, a.sdo.t, nqb * kBlk, T);
     }
-    bwd_block<D, CAUSAL, DROP>(a, Qs, dOs, lse2, dl, kf, vf, dk, dv, static_cast<uint32_t>(bh), q0, k0, mykey, kvalid,
-                               KMp != nullptr);
+    bwd_block<D, MODE, DROP>(a, Qs, dOs, lse2, dl, kf, vf, dk, dv, static_cast<uint32_t>(bh), q0, k0, mykey, kvalid,
+                             KMp != nullptr, qlo, qhi, kr);
     h = nh;
     qb = nqb;
   }
@@ -689,11 +808,13 @@ struct DqArgs {
   int H, T, G;
   float scale, scale_log2;
   KeyMaskDrop md;
+  Band band;
 };
 
 // dQ for a block of kFwdRows query rows (same wave / lane layout as the forward).
-template <int D, int kQT, bool CAUSAL, bool DROP>
+template <int D, int kQT, int MODE, bool DROP>
 __global__ void __launch_bounds__(kThreads) attn_dq_kernel(DqArgs a) {
+  constexpr bool CAUSAL = MODE == kCausal, BAND = MODE == kBand;
   constexpr int kFwdRows = fwd_rows(kQT);
   constexpr int KP = kLdsStride(D);
   __shared__ __attribute__((aligned(16))) bf16_t Ks[kBlk * KP];
@@ -714,9 +835,14 @@ __global__ void __launch_bounds__(kThreads) attn_dq_kernel(DqArgs a) {
 
   s8 qf[kQT][D / 32], of[kQT][D / 32];
   float lse2[kQT], dl[kQT];
+  int klo[kQT], khi[kQT];  // band: the lane's key range, one per 16-row tile
 #pragma unroll
   for (int qt = 0; qt < kQT; ++qt) {
     const int q = qw + qt * 16 + c;
+    if constexpr (BAND) {  // q < padded row length
+      klo[qt] = a.band.klo[b * a.band.bs + q];
+      khi[qt] = min(a.band.khi[b * a.band.bs + q], T);
+    }
 #pragma unroll
     for (int ds = 0; ds < D / 32; ++ds) {
       s8 x = {0, 0, 0, 0, 0, 0, 0, 0}, y = x;
@@ -736,11 +862,13 @@ __global__ void __launch_bounds__(kThreads) attn_dq_kernel(DqArgs a) {
 #pragma unroll
     for (int dt = 0; dt < D / 16; ++dt) dq[qt][dt] = f4{0.f, 0.f, 0.f, 0.f};
 
-  const int kb_end = CAUSAL ? min(nkb, (q0 + kFwdRows - 1) / kBlk + 1) : nkb;
+  KeyTiles bt = {0, 0, 0, 0};
+  if constexpr (BAND) bt = band_key_tiles(a.band.klo + b * a.band.bs, a.band.khi + b * a.band.bs, q0, kFwdRows, T);
+  const int kb_end = BAND ? bt.end : CAUSAL ? min(nkb, (q0 + kFwdRows - 1) / kBlk + 1) : nkb;
   Stage<D, kBlk> ks, vs;
-  ks.load(Kp, a.sk.t, 0, T);
-  vs.load(Vp, a.sv.t, 0, T);
-  for (int kb = 0; kb < kb_end; ++kb) {
+  ks.load(Kp, a.sk.t, bt.begin * kBlk, T);
+  vs.load(Vp, a.sv.t, bt.begin * kBlk, T);
+  for (int kb = bt.begin; kb < kb_end; ++kb) {
     const int k0 = kb * kBlk;
     __syncthreads();
     ks.store(Ks);
@@ -769,7 +897,8 @@ __global__ void __launch_bounds__(kThreads) attn_dq_kernel(DqArgs a) {
         }
       }
     }
-    const bool need_mask = (k0 + kBlk > T) || (CAUSAL && k0 + kBlk - 1 > qw);
+    const bool need_mask = (k0 + kBlk > T) || (CAUSAL && k0 + kBlk - 1 > qw) ||
+                           (BAND && (kb < bt.full_lo || kb >= bt.full_hi));
 #pragma unroll
     for (int qt = 0; qt < kQT; ++qt) {
       const int myq = qw + qt * 16 + c;
@@ -781,7 +910,7 @@ __global__ void __launch_bounds__(kThreads) attn_dq_kernel(DqArgs a) {
         for (int r = 0; r < 4; ++r) {
           const int key = k0 + nt * 16 + 4 * g + r;
           float p = ex2(fmaf(s[qt][nt][r], a.scale_log2, -lse2[qt]));
-          if (need_mask) p = (key > kmax) ? 0.f : p;
+          if (need_mask) p = (BAND ? (key < klo[qt] || key >= khi[qt]) : key > kmax) ? 0.f : p;
           p = ((mw >> (8 * r)) & 0xffu) ? p : 0.f;
           float dpv = dp[qt][nt][r];
           if constexpr (DROP)
@@ -830,12 +959,15 @@ extern "C" {
 
 #define DAMD_ATTN_DISPATCH_D(KERNEL, D_, GRID, ARGS)                                                \
   do {                                                                                               \
-    if (causal) {                                                                                    \
-      if ((ARGS).md.thresh != 0) DAMD_LAUNCH((KERNEL<D_, true, true>), GRID, dim3(kThreads), 0, st, ARGS); \
-      else DAMD_LAUNCH((KERNEL<D_, true, false>), GRID, dim3(kThreads), 0, st, ARGS);                \
+    if ((ARGS).band.klo != nullptr) {                                                                \
+      if ((ARGS).md.thresh != 0) DAMD_LAUNCH((KERNEL<D_, kBand, true>), GRID, dim3(kThreads), 0, st, ARGS); \
+      else DAMD_LAUNCH((KERNEL<D_, kBand, false>), GRID, dim3(kThreads), 0, st, ARGS);               \
+    } else if (causal) {                                                                             \
+      if ((ARGS).md.thresh != 0) DAMD_LAUNCH((KERNEL<D_, kCausal, true>), GRID, dim3(kThreads), 0, st, ARGS); \
+      else DAMD_LAUNCH((KERNEL<D_, kCausal, false>), GRID, dim3(kThreads), 0, st, ARGS);             \
     } else {                                                                                         \
-      if ((ARGS).md.thresh != 0) DAMD_LAUNCH((KERNEL<D_, false, true>), GRID, dim3(kThreads), 0, st, ARGS); \
-      else DAMD_LAUNCH((KERNEL<D_, false, false>), GRID, dim3(kThreads), 0, st, ARGS);               \
+      if ((ARGS).md.thresh != 0) DAMD_LAUNCH((KERNEL<D_, kFull, true>), GRID, dim3(kThreads), 0, st, ARGS); \
+      else DAMD_LAUNCH((KERNEL<D_, kFull, false>), GRID, dim3(kThreads), 0, st, ARGS);               \
     }                                                                                                \
   } while (0)
 
@@ -905,10 +1037,14 @@ int damd_attn_gqa_split(int B, int Hkv, int G, int T) {
 }
 
 // strides: 4 tensors (q, k, v, o) x (b, h, t) in elements; km: optional [B][kms] key mask.
+// klo .. qhi: the band arrays (all four or none; with them `causal` only feeds attn_qt), rows of
+// band_stride int32 (0: one shared row), padded to a multiple of 128 entries >= T.
 // k, v have Hkv heads, H % Hkv == 0 (checked by the binding).
 void damd_attn_fwd_launch(const void* q, const void* k, const void* v, void* o, float* lse, const int64_t* strides,
                           int B, int H, int Hkv, int T, int D, float scale, int causal, const uint8_t* km,
-                          int64_t kms, uint32_t seed, const int64_t* seedp, float drop_p, hipStream_t st) {
+                          int64_t kms, uint32_t seed, const int64_t* seedp, float drop_p, hipStream_t st,
+                          const int32_t* klo, const int32_t* khi, const int32_t* qlo, const int32_t* qhi,
+                          int64_t band_stride) {
   FwdArgs a;
   a.q = static_cast<const bf16_t*>(q); a.k = static_cast<const bf16_t*>(k); a.v = static_cast<const bf16_t*>(v);
   a.o = static_cast<bf16_t*>(o); a.lse = lse;
@@ -916,6 +1052,7 @@ void damd_attn_fwd_launch(const void* q, const void* k, const void* v, void* o, 
   a.sv = {strides[6], strides[7], strides[8]}; a.so = {strides[9], strides[10], strides[11]};
   a.H = H; a.T = T; a.G = H / Hkv; a.scale_log2 = scale * kLog2e;
   a.md = make_md(km, kms, seed, seedp, drop_p);
+  a.band = {klo, khi, qlo, qhi, band_stride};
   const int qt = attn_qt(false, B, H, T, D, causal), rows = fwd_rows(qt);
   dim3 grid(((T + rows - 1) / rows) * H * B);
   DAMD_ATTN_DISPATCH_QT(attn_fwd_kernel, qt, grid, a);
@@ -928,7 +1065,8 @@ void damd_attn_bwd_launch(const void* q, const void* k, const void* v, const voi
                           const float* lse, float* delta, float* part, int split, void* dq, void* dk, void* dv,
                           const int64_t* s, int B, int H, int Hkv, int T, int D, float scale, int causal,
                           const uint8_t* km, int64_t kms, uint32_t seed, const int64_t* seedp, float drop_p,
-                          hipStream_t st) {
+                          hipStream_t st, const int32_t* klo, const int32_t* khi, const int32_t* qlo,
+                          const int32_t* qhi, int64_t band_stride) {
   const Strides sq{s[0], s[1], s[2]}, sk{s[3], s[4], s[5]}, sv{s[6], s[7], s[8]}, so{s[9], s[10], s[11]},
       sdo{s[12], s[13], s[14]}, sdk{s[15], s[16], s[17]}, sdv{s[18], s[19], s[20]}, sdq{s[21], s[22], s[23]};
   const int64_t rows = static_cast<int64_t>(B) * H * T;
@@ -951,6 +1089,7 @@ void damd_attn_bwd_launch(const void* q, const void* k, const void* v, const voi
   a.H = H; a.T = T; a.scale = scale; a.scale_log2 = scale * kLog2e;
   a.G = H / Hkv; a.S = a.G > 1 ? split : 1; a.part = part;
   a.md = make_md(km, kms, seed, seedp, drop_p);
+  a.band = {klo, khi, qlo, qhi, band_stride};
   const int nblk = (T + kBlk - 1) / kBlk;
   if (a.G == 1) {
     dim3 grid(nblk * H * B);
@@ -971,6 +1110,7 @@ void damd_attn_bwd_launch(const void* q, const void* k, const void* v, const voi
   d.sq = sq; d.sk = sk; d.sv = sv; d.sdo = sdo; d.sdq = sdq;
   d.H = H; d.T = T; d.G = a.G; d.scale = scale; d.scale_log2 = scale * kLog2e;
   d.md = a.md;
+  d.band = a.band;
   const int qt = attn_qt(true, B, H, T, D, causal), qrows = fwd_rows(qt);
   dim3 qgrid(((T + qrows - 1) / qrows) * H * B);
   DAMD_ATTN_DISPATCH_QT(attn_dq_kernel, qt, qgrid, d);

@@ -182,12 +182,14 @@ extern "C" void damd_stem_wgrad_launch(const void*, const void*, float*, void*, 
 // launchers (attention.hip)
 extern "C" void damd_attn_fwd_launch(const void*, const void*, const void*, void*, float*, const int64_t*, int, int,
                                      int, int, int, float, int, const uint8_t*, int64_t, uint32_t, const int64_t*,
-                                     float, hipStream_t);
+                                     float, hipStream_t, const int32_t*, const int32_t*, const int32_t*,
+                                     const int32_t*, int64_t);
 extern "C" int damd_attn_gqa_split(int, int, int, int);
 extern "C" void damd_attn_bwd_launch(const void*, const void*, const void*, const void*, const void*, const float*,
                                      float*, float*, int, void*, void*, void*, const int64_t*, int, int, int, int, int,
                                      float, int, const uint8_t*, int64_t, uint32_t, const int64_t*, float,
-                                     hipStream_t);
+                                     hipStream_t, const int32_t*, const int32_t*, const int32_t*, const int32_t*,
+                                     int64_t);
 // launchers (fused.hip)
 extern "C" void damd_lm_ce_fwd_launch(const void*, const int64_t*, int64_t, int, int, int, int64_t, float*, float*,
                                       hipStream_t);
@@ -1504,15 +1506,43 @@ const uint8_t* check_kmask(const c10::optional<at::Tensor>& km, const at::Tensor
   return m.data_ptr<uint8_t>();
 }
 
+// Optional band mask: int32 [4 (klo, khi, qlo, qhi), Bb, Tpad] with Bb in {1, B} (1: every batch
+// row shares the ranges), contiguous, Tpad >= T a multiple of 128; entries past T hold empty ranges.
+// Query q attends the keys [klo[q], khi[q]), key k is attended by the queries [qlo[k], qhi[k]).
+// Preconditions of the raw binding, NOT checked here (ops.attention.band_ranges meets them): all
+// four bounds are non-decreasing along a row, the (klo, khi) and (qlo, qhi) planes describe the
+// same set of (q, k) pairs, and entries past T are empty (lo >= hi).  The kernels derive the tiles
+// they visit from the first and last row of a block, so an array that breaks these silently skips
+// tiles it needed (wrong numbers, no fault: the tile ranges are clamped to the tensor).
+struct BandPtrs {
+  const int32_t* p[4] = {nullptr, nullptr, nullptr, nullptr};
+  int64_t stride = 0;
+};
+BandPtrs check_band(const c10::optional<at::Tensor>& band, const at::Tensor& q) {
+  BandPtrs r;
+  if (!band.has_value() || !band->defined()) return r;
+  const at::Tensor& m = *band;
+  TORCH_CHECK(m.is_cuda() && m.scalar_type() == at::kInt && m.dim() == 3 && m.is_contiguous(),
+              "band: contiguous int32 [4, B or 1, Tpad]");
+  TORCH_CHECK(m.size(0) == 4 && (m.size(1) == q.size(0) || m.size(1) == 1) && m.size(2) >= q.size(2) &&
+                  m.size(2) % 128 == 0,
+              "band: [4, B or 1, Tpad] with Tpad >= T a multiple of 128");
+  TORCH_CHECK(m.device() == q.device(), "band on another device");
+  for (int i = 0; i < 4; ++i) r.p[i] = m.data_ptr<int32_t>() + i * m.stride(0);
+  r.stride = m.size(1) == 1 ? 0 : m.stride(1);
+  return r;
+}
+
 std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, bool causal,
                                  double scale, const c10::optional<at::Tensor>& kmask, double drop_p, int64_t seed,
-                                 const c10::optional<at::Tensor>& seed_t) {
+                                 const c10::optional<at::Tensor>& seed_t, const c10::optional<at::Tensor>& band) {
   check_attn(q, q, "q");
   check_attn_kv(k, q);
   check_attn(v, k, "v");
   TORCH_CHECK(drop_p >= 0.0 && drop_p < 1.0, "dropout probability must be in [0, 1)");
   int64_t kms = 0;
   const uint8_t* km = check_kmask(kmask, q, &kms);
+  const BandPtrs bp = check_band(band, q);
   const int64_t B = q.size(0), H = q.size(1), T = q.size(2), D = q.size(3);
   // output in [B, T, H, D] memory (so "merge heads" is a free view), returned as [B, H, T, D]
   auto o = at::empty({B, T, H, D}, q.options()).permute({0, 2, 1, 3});
@@ -1526,14 +1556,15 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const
     damd_attn_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), s.data(),
                          static_cast<int>(B), static_cast<int>(H), static_cast<int>(k.size(1)), static_cast<int>(T),
                          static_cast<int>(D), static_cast<float>(scale), causal ? 1 : 0, km, kms,
-                         static_cast<uint32_t>(seed), seed_ptr(seed_t, q), static_cast<float>(drop_p), cur_stream());
+                         static_cast<uint32_t>(seed), seed_ptr(seed_t, q), static_cast<float>(drop_p), cur_stream(),
+                         bp.p[0], bp.p[1], bp.p[2], bp.p[3], bp.stride);
   return {o, lse};
 }
 
 void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
               const at::Tensor& o, const at::Tensor& lse, at::Tensor& dq, at::Tensor& dk, at::Tensor& dv, bool causal,
               double scale, const c10::optional<at::Tensor>& kmask, double drop_p, int64_t seed,
-              const c10::optional<at::Tensor>& seed_t) {
+              const c10::optional<at::Tensor>& seed_t, const c10::optional<at::Tensor>& band) {
   check_attn(q, q, "q");
   check_attn_kv(k, q);
   check_attn(v, k, "v");
@@ -1547,6 +1578,7 @@ void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, 
   auto delta = at::empty({B, H, T}, lse.options());
   int64_t kms = 0;
   const uint8_t* km = check_kmask(kmask, q, &kms);
+  const BandPtrs bp = check_band(band, q);
   // grouped-query dK/dV with the group's heads split over `split` workgroups: fp32 partials
   int split = 1;
   at::Tensor part;
@@ -1565,7 +1597,8 @@ void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, 
                          part.defined() ? part.data_ptr<float>() : nullptr, split, dq.data_ptr(), dk.data_ptr(),
                          dv.data_ptr(), s.data(), static_cast<int>(B), static_cast<int>(H), static_cast<int>(Hkv),
                          static_cast<int>(T), static_cast<int>(D), static_cast<float>(scale), causal ? 1 : 0, km, kms,
-                         static_cast<uint32_t>(seed), seed_ptr(seed_t, q), static_cast<float>(drop_p), cur_stream());
+                         static_cast<uint32_t>(seed), seed_ptr(seed_t, q), static_cast<float>(drop_p), cur_stream(),
+                         bp.p[0], bp.p[1], bp.p[2], bp.p[3], bp.stride);
 }
 
 // ---------------------------------------------------------------- fused LM loss / bias grad
@@ -1797,10 +1830,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gelu_bwd_bias", &gelu_bwd_bias, py::arg("dg"), py::arg("h"), py::arg("bias_dtype"), py::arg("exact") = false);
   m.def("attn_supported", &attn_supported);
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("scale"),
-        py::arg("kmask") = py::none(), py::arg("drop_p") = 0.0, py::arg("seed") = 0, py::arg("seed_t") = py::none());
+        py::arg("kmask") = py::none(), py::arg("drop_p") = 0.0, py::arg("seed") = 0, py::arg("seed_t") = py::none(),
+        py::arg("band") = py::none());
   m.def("attn_bwd", &attn_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("causal"), py::arg("scale"),
-        py::arg("kmask") = py::none(), py::arg("drop_p") = 0.0, py::arg("seed") = 0, py::arg("seed_t") = py::none());
+        py::arg("kmask") = py::none(), py::arg("drop_p") = 0.0, py::arg("seed") = 0, py::arg("seed_t") = py::none(),
+        py::arg("band") = py::none());
   m.def("bn_supported", &bn_supported);
   m.def("bn_act_fwd", &bn_act_fwd);
   m.def("bn_act_bwd", &bn_act_bwd);

@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from torch import nn
 from torch.utils.checkpoint import checkpoint
 
-from determined_amd.ops.attention import qkv_attention
+from determined_amd.ops.attention import band_ranges, qkv_attention
 from determined_amd.ops.fused import FusedLinear, linear_gelu, lm_cross_entropy
 from determined_amd.ops.norm import FusedLayerNorm
 
@@ -69,12 +69,14 @@ class CausalSelfAttention(nn.Module):
         self.attn_dropout = cfg.attn_dropout
         self.resid_drop = nn.Dropout(cfg.dropout)
 
-    def forward(self, x: torch.Tensor, residual_dropout: bool = True) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, residual_dropout: bool = True,
+                band: Optional[torch.Tensor] = None) -> torch.Tensor:
         B, T, C = x.shape
         qkv = self.c_attn(x).view(B, T, 3, self.n_head, C // self.n_head)
         # fused MFMA flash attention on the packed projection; returns [B, H, T, D] laid out
         # as [B, T, H, D], so merging the heads below is a view
-        y = qkv_attention(qkv, causal=True, dropout_p=self.attn_dropout if self.training else 0.0)
+        # (band: the kernels' band mask of packed documents, built once per forward from segment_ids)
+        y = qkv_attention(qkv, causal=True, dropout_p=self.attn_dropout if self.training else 0.0, band=band)
         y = y.transpose(1, 2).reshape(B, T, C)
         out = self.c_proj(y)
         return self.resid_drop(out) if residual_dropout else out
@@ -100,15 +102,15 @@ class Block(nn.Module):
         self.ln_2 = FusedLayerNorm(cfg.n_embd, eps=cfg.layer_norm_epsilon)
         self.mlp = MLP(cfg)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x = x + self.attn(self.ln_1(x))
+    def forward(self, x: torch.Tensor, band: Optional[torch.Tensor] = None) -> torch.Tensor:
+        x = x + self.attn(self.ln_1(x), band=band)
         return x + self.mlp(self.ln_2(x))
 
-    def forward_fused(self, x: torch.Tensor, h1: torch.Tensor, p: float):
+    def forward_fused(self, x: torch.Tensor, h1: torch.Tensor, p: float, band: Optional[torch.Tensor] = None):
         """Given the residual stream ``x`` and ``h1 = ln_1(x)``: returns ``(x', m)`` where
         ``x' = x + dropout(attn(h1))`` (fused with ``ln_2``) and ``m`` is the MLP branch whose
         residual add + dropout the caller fuses into the next LayerNorm."""
-        a = self.attn(h1, residual_dropout=False)
+        a = self.attn(h1, residual_dropout=False, band=band)
         x, h2 = self.ln_2(x, branch=a, p=p)
         return x, self.mlp(h2, residual_dropout=False)
 
@@ -154,14 +156,21 @@ class GPT2LMHeadModel(nn.Module):
             n -= self.wte.weight.numel() + self.wpe.weight.numel()
         return n
 
-    def hidden_states(self, input_ids: torch.Tensor) -> torch.Tensor:
+    def hidden_states(self, input_ids: torch.Tensor, segment_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``segment_ids [B, T]``: packed documents (maximal runs of equal ids) -- positions restart
+        at each document start and attention stays inside the token's document (one band tensor,
+        built here, serves every block)."""
         B, T = input_ids.shape
         pos = torch.arange(T, device=input_ids.device)
+        band = None
+        if segment_ids is not None:
+            band = band_ranges(T, True, None, segment_ids)
+            pos = pos - band[0, :, :T]  # klo: the document start
         x = self.drop(self.wte(input_ids) + self.wpe(pos))
         ckpt = self.config.activation_checkpointing and self.training
         if not x.is_cuda:
             for blk in self.h:
-                x = checkpoint(blk, x, use_reentrant=False) if ckpt else blk(x)
+                x = checkpoint(blk, x, band, use_reentrant=False) if ckpt else blk(x, band)
             return self.ln_f(x)
         # every residual add + dropout is fused into the following LayerNorm kernel
         # (ln_2 of the same block, ln_1 of the next, ln_f after the last)
@@ -169,16 +178,18 @@ class GPT2LMHeadModel(nn.Module):
         h = self.h[0].ln_1(x)
         for i, blk in enumerate(self.h):
             if ckpt:
-                x, m = checkpoint(blk.forward_fused, x, h, p, use_reentrant=False)
+                x, m = checkpoint(blk.forward_fused, x, h, p, band, use_reentrant=False)
             else:
-                x, m = blk.forward_fused(x, h, p)
+                x, m = blk.forward_fused(x, h, p, band)
             nxt = self.h[i + 1].ln_1 if i + 1 < len(self.h) else self.ln_f
             x, h = nxt(x, branch=m, p=p)
         return h
 
-    def forward(self, input_ids: torch.Tensor, labels: Optional[torch.Tensor] = None) -> Any:
-        """Returns logits ``[B, T, vocab]`` or, with ``labels``, the mean next-token loss."""
-        h = self.hidden_states(input_ids)
+    def forward(self, input_ids: torch.Tensor, labels: Optional[torch.Tensor] = None,
+                segment_ids: Optional[torch.Tensor] = None) -> Any:
+        """Returns logits ``[B, T, vocab]`` or, with ``labels``, the mean next-token loss.
+        ``segment_ids``: packed documents (see ``hidden_states``)."""
+        h = self.hidden_states(input_ids, segment_ids)
         logits = F.linear(h, self.wte.weight)  # tied LM head
         if labels is None:
             return logits[..., : self.config.vocab_size]

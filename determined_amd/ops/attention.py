@@ -10,6 +10,13 @@ summed over each group inside the dK/dV kernel.  ``qkv_attention`` (MHA only) ta
 writes dQ/dK/dV into ONE gradient buffer of that shape, so the backward needs no concatenation of
 three gradients.
 
+Band masks (``window=`` / ``segment_ids=``): sliding-window attention (query ``q`` sees the keys
+``q - window + 1 .. q``) and packed documents (several sequences in one ``[B, T]`` row; attention
+never crosses a document boundary) are both a staircase -- query ``q`` attends one contiguous key
+range whose bounds do not decrease with ``q``.  ``band_ranges`` builds the four int32 arrays that
+describe it on the device, and the kernels' third mask mode visits only the key tiles / query blocks
+inside the band: O(T * W) work, no mask tensor, composable with ``key_padding`` and dropout.
+
 Anything else (CPU tensors, fp32, other head sizes) uses PyTorch's ``scaled_dot_product_attention``
 -- on ROCm with the composable-kernel backend preferred.
 """
@@ -57,6 +64,92 @@ def key_mask(valid: torch.Tensor) -> torch.Tensor:
     return km
 
 
+def segment_bounds(segment_ids: torch.Tensor):
+    """``(start, end)``, int64 ``[B, T]``: each token's document is the tokens ``start <= t < end``
+    (a document is a maximal run of equal ids)."""
+    T = segment_ids.shape[1]
+    ar = torch.arange(T, device=segment_ids.device)
+    change = torch.ones_like(segment_ids, dtype=torch.bool)  # first token of a document
+    change[:, 1:] = segment_ids[:, 1:] != segment_ids[:, :-1]
+    last = torch.ones_like(change)  # last token of a document
+    last[:, :-1] = change[:, 1:]
+    start = torch.cummax(torch.where(change, ar, 0), dim=1).values
+    end = torch.cummin(torch.where(last, ar + 1, T).flip(1), dim=1).values.flip(1)
+    return start, end
+
+
+def band_ranges(T: int, causal: bool, window: Optional[int] = None, segment_ids: Optional[torch.Tensor] = None,
+                device=None) -> torch.Tensor:
+    """The kernels' band mask as one int32 ``[4, Bb, Tpad]`` tensor ``(klo, khi, qlo, qhi)``: query
+    ``q`` attends the keys ``klo[q] <= k < khi[q]`` and key ``k`` is attended by the queries ``qlo[k]
+    <= q < qhi[k]`` (the same mask seen from the key).  ``segment_ids [B, T]``: a document is a
+    maximal run of equal ids; without it ``Bb = 1`` (one row serves every batch element).  Rows are
+    padded to a multiple of 128 with empty ranges.  Device ops only -- no host synchronisation, so a
+    captured step may call it."""
+    if window is not None and not causal:
+        raise ValueError("window= needs causal=True")
+    if window is not None and window < 1:
+        raise ValueError("window must be >= 1")
+    if segment_ids is not None:
+        if segment_ids.dim() != 2 or segment_ids.shape[1] != T:
+            raise ValueError("segment_ids must be [B, T]")
+        device = segment_ids.device
+    ar = torch.arange(T, device=device)
+    if segment_ids is not None:
+        start, end = segment_bounds(segment_ids)
+    else:
+        start, end = torch.zeros(1, T, dtype=torch.long, device=device), torch.full((1, T), T, device=device)
+    klo, khi, qlo, qhi = start, end, start, end
+    if causal:
+        khi, qlo = (ar + 1).expand_as(end), ar.expand_as(start)
+    if window is not None:
+        klo, qhi = torch.maximum(klo, ar - window + 1), torch.minimum(qhi, ar + window)
+    out = torch.zeros(4, start.shape[0], (T + 127) // 128 * 128, dtype=torch.int32, device=device)
+    out[:, :, :T] = torch.stack((klo, khi, qlo, qhi))
+    return out
+
+
+def band_mask(band: torch.Tensor, T: int) -> torch.Tensor:
+    """The dense boolean ``[Bb, 1, T, T]`` mask (True = attend) of a ``band_ranges`` tensor."""
+    ar = torch.arange(T, device=band.device)
+    return ((ar >= band[0, :, :T, None]) & (ar < band[1, :, :T, None]))[:, None]
+
+
+_window_bands: dict = {}  # (T, window, device) -> band_ranges tensor of a pure sliding window
+
+
+def _band(T: int, causal: bool, window, segment_ids, device, band=None) -> Optional[torch.Tensor]:
+    """The band tensor of one attention call, or None when the mask is plain full / causal: a
+    prebuilt ``band`` as it is; a pure window from a small cache (it depends on ``(T, window)``
+    only, so every layer and every step share one tensor -- not filled during a stream capture,
+    whose allocations belong to the graph); ``segment_ids`` through ``band_ranges``."""
+    if band is not None:
+        return band
+    if segment_ids is not None:
+        return band_ranges(T, causal, window, segment_ids, device)
+    if window is None or (causal and window >= T):
+        return None
+    key = (T, window, str(device))
+    if key not in _window_bands:
+        b = band_ranges(T, causal, window, None, device)
+        if b.is_cuda and torch.cuda.is_current_stream_capturing():
+            return b
+        _window_bands[key] = b
+    return _window_bands[key]
+
+
+def _sdpa_band(q, k, v, band, key_padding, dropout_p, scale):
+    """SDPA with the band as a dense mask (tensors the kernels do not serve)."""
+    T = q.shape[2]
+    mask = band_mask(band, T)
+    if key_padding is not None:
+        mask = mask & key_padding[:, None, None, :T].bool()
+    if q.is_cuda:
+        _configure()
+    return F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=dropout_p, scale=scale,
+                                          enable_gqa=k.shape[1] != q.shape[1])
+
+
 def _mix64(x: int) -> int:
     """splitmix64 finaliser (host ints)."""
     x = (x + 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
@@ -94,10 +187,11 @@ def dropout_seed(dropout_p: float, device: torch.device):
 
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal: bool, scale: float, km=None, dropout_p: float = 0.0, seed=(0, None)):
-        o, lse = _ext().attn_fwd(q, k, v, causal, scale, km, dropout_p, seed[0], seed[1])
+    def forward(ctx, q, k, v, causal: bool, scale: float, km=None, dropout_p: float = 0.0, seed=(0, None),
+                band=None):
+        o, lse = _ext().attn_fwd(q, k, v, causal, scale, km, dropout_p, seed[0], seed[1], band)
         ctx.save_for_backward(q, k, v, o, lse)
-        ctx.causal, ctx.scale, ctx.km, ctx.dropout_p, ctx.seed = causal, scale, km, dropout_p, seed
+        ctx.causal, ctx.scale, ctx.km, ctx.dropout_p, ctx.seed, ctx.band = causal, scale, km, dropout_p, seed, band
         return o
 
     @staticmethod
@@ -114,19 +208,19 @@ class _FlashAttnFn(torch.autograd.Function):
             dq = torch.empty(B, T, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
             dk, dv = torch.empty(2, B, T, Hkv, D, dtype=q.dtype, device=q.device).permute(0, 1, 3, 2, 4).unbind(0)
         _ext().attn_bwd(do, q, k, v, o, lse, dq, dk, dv, ctx.causal, ctx.scale, ctx.km, ctx.dropout_p, ctx.seed[0],
-                        ctx.seed[1])
-        return dq, dk, dv, None, None, None, None, None
+                        ctx.seed[1], ctx.band)
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 class _QKVFlashAttnFn(torch.autograd.Function):
     """Attention over a packed ``[B, T, 3, H, D]`` tensor; gradient is packed the same way."""
 
     @staticmethod
-    def forward(ctx, qkv, causal: bool, scale: float, dropout_p: float = 0.0, seed=(0, None), km=None):
+    def forward(ctx, qkv, causal: bool, scale: float, dropout_p: float = 0.0, seed=(0, None), km=None, band=None):
         q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
-        o, lse = _ext().attn_fwd(q, k, v, causal, scale, km, dropout_p, seed[0], seed[1])
+        o, lse = _ext().attn_fwd(q, k, v, causal, scale, km, dropout_p, seed[0], seed[1], band)
         ctx.save_for_backward(qkv, o, lse)
-        ctx.causal, ctx.scale, ctx.dropout_p, ctx.seed, ctx.km = causal, scale, dropout_p, seed, km
+        ctx.causal, ctx.scale, ctx.dropout_p, ctx.seed, ctx.km, ctx.band = causal, scale, dropout_p, seed, km, band
         return o
 
     @staticmethod
@@ -138,33 +232,51 @@ class _QKVFlashAttnFn(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         dq, dk, dv = (dqkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
         _ext().attn_bwd(do, q, k, v, o, lse, dq, dk, dv, ctx.causal, ctx.scale, ctx.km, ctx.dropout_p, ctx.seed[0],
-                        ctx.seed[1])
-        return dqkv, None, None, None, None, None
+                        ctx.seed[1], ctx.band)
+        return dqkv, None, None, None, None, None, None
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
                     scale: Optional[float] = None, key_padding: Optional[torch.Tensor] = None,
-                    dropout_p: float = 0.0) -> torch.Tensor:
+                    dropout_p: float = 0.0, window: Optional[int] = None,
+                    segment_ids: Optional[torch.Tensor] = None, band: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused attention for ``[B, H, T, D]`` bf16 tensors on the GPU (raises if unsupported).
     ``k`` / ``v`` may have ``Hkv`` heads with ``H % Hkv == 0`` (grouped-query / multi-query
     attention: query head ``h`` reads K/V head ``h // (H // Hkv)``; their gradients have ``Hkv``
     heads).  ``key_padding``: a ``key_mask`` tensor (or a ``[B, T]`` validity mask);
-    ``dropout_p``: attention-probability dropout (in-kernel)."""
+    ``dropout_p``: attention-probability dropout (in-kernel).  ``window`` (needs ``causal``): query
+    ``q`` sees the keys ``q - window + 1 .. q``; ``segment_ids [B, T]``: packed documents (maximal
+    runs of equal ids), attention stays inside the query's document; ``band``: the prebuilt
+    ``band_ranges`` tensor in their place (a model builds it once per forward and hands it to every
+    layer).  With any of the three, tensors the kernels do not serve go through SDPA with the same
+    mask instead of raising."""
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else scale
+    if window is not None or segment_ids is not None:
+        band = _band(q.shape[2], causal, window, segment_ids, q.device, band)
+    if band is not None and not _supported(q, k, v):
+        return _sdpa_band(q, k, v, band, key_padding, dropout_p, float(scale))
     if not _supported(q, k, v):
         raise ValueError("flash_attention needs bf16 GPU tensors [B,H,T,D] with D in {64,128} and a contiguous D")
     if key_padding is not None and (key_padding.dtype != torch.uint8 or key_padding.shape[1] % 64):
         key_padding = key_mask(key_padding)
     return _FlashAttnFn.apply(q, k, v, causal, float(scale), key_padding, float(dropout_p),
-                              dropout_seed(dropout_p, q.device))
+                              dropout_seed(dropout_p, q.device), band)
 
 
-def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dropout_p: float = 0.0) -> torch.Tensor:
+def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dropout_p: float = 0.0,
+                     window: Optional[int] = None, segment_ids: Optional[torch.Tensor] = None,
+                     band: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``softmax(q k^T / sqrt(d) + causal_mask) v`` for ``[B, H, T, D]`` tensors; ``k`` / ``v`` may be
-    ``[B, Hkv, T, D]`` with ``H % Hkv == 0`` (grouped-query attention)."""
+    ``[B, Hkv, T, D]`` with ``H % Hkv == 0`` (grouped-query attention).  ``window`` / ``segment_ids``:
+    sliding-window / packed-document masks on top of the causal one, or the prebuilt ``band`` (see
+    ``flash_attention``)."""
+    if window is not None or segment_ids is not None:
+        band = _band(q.shape[2], True, window, segment_ids, q.device, band)
     if q.is_cuda and _supported(q, k, v):
         return _FlashAttnFn.apply(q, k, v, True, 1.0 / math.sqrt(q.shape[-1]), None, float(dropout_p),
-                                  dropout_seed(dropout_p, q.device))
+                                  dropout_seed(dropout_p, q.device), band)
+    if band is not None:
+        return _sdpa_band(q, k, v, band, None, dropout_p, None)
     if q.is_cuda:
         _configure()
     return F.scaled_dot_product_attention(q, k, v, dropout_p=dropout_p, is_causal=True,
@@ -172,18 +284,25 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dropout_
 
 
 def qkv_attention(qkv: torch.Tensor, causal: bool = True, dropout_p: float = 0.0,
-                  key_padding: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> torch.Tensor:
+                  key_padding: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                  window: Optional[int] = None, segment_ids: Optional[torch.Tensor] = None,
+                  band: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Attention over the packed projection ``qkv [B, T, 3, H, D]``; returns ``[B, H, T, D]``
     whose memory is ``[B, T, H, D]`` (merging heads afterwards is a free view).  ``key_padding``:
-    the kernels' uint8 key mask (``key_mask``) or None."""
+    the kernels' uint8 key mask (``key_mask``) or None.  ``window`` / ``segment_ids`` / ``band``: see
+    ``flash_attention``."""
     B, T, _, H, D = qkv.shape
     scale = 1.0 / math.sqrt(D) if scale is None else float(scale)
+    if window is not None or segment_ids is not None:
+        band = _band(T, causal, window, segment_ids, qkv.device, band)
     if qkv.is_cuda and qkv.is_contiguous() and qkv.dtype == torch.bfloat16 and D in (64, 128):
         if key_padding is not None and (key_padding.dtype != torch.uint8 or key_padding.shape[1] % 64):
             key_padding = key_mask(key_padding)
         return _QKVFlashAttnFn.apply(qkv, causal, scale, float(dropout_p), dropout_seed(dropout_p, qkv.device),
-                                     key_padding)
+                                     key_padding, band)
     q, k, v = qkv.permute(2, 0, 3, 1, 4).unbind(0)
+    if band is not None:
+        return _sdpa_band(q, k, v, band, key_padding, dropout_p, scale)
     if qkv.is_cuda:
         _configure()
     mask = None

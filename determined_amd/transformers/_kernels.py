@@ -7,7 +7,9 @@
   attention-probability dropout), registered as the ``"damd"`` attention implementation through
   ``AttentionInterface`` together with a mask function that hands the kernel its uint8 key mask
   (built once per forward, ``None`` for unpadded batches).  Grouped-query / multi-query decoders
-  pass their un-repeated ``[B, Hkv, T, D]`` key / value straight to the grouped-query kernels;
+  pass their un-repeated ``[B, Hkv, T, D]`` key / value straight to the grouped-query kernels, and
+  sliding-window layers (``sliding_window=`` from Mistral / Qwen2-style attention) run the kernels'
+  band mode (``window=``);
 * ``LlamaRMSNorm`` / ``MistralRMSNorm`` / ``Qwen2RMSNorm`` -> ``FusedRMSNorm`` (``csrc/norm.hip``);
 * ``BertSelfOutput`` / ``BertOutput`` (dense -> dropout -> LayerNorm(. + residual)) -> the dense GEMM
   followed by ONE ``csrc/norm.hip`` kernel doing residual add + dropout + LayerNorm (its backward
@@ -55,9 +57,11 @@ def _damd_mask(batch_size: int, q_length: int, kv_length: int, q_offset: int = 0
 
 def _damd_attention(module: nn.Module, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor,
                     attention_mask: Optional[torch.Tensor], dropout: float = 0.0, scaling: Optional[float] = None,
-                    is_causal: Optional[bool] = None, **kwargs: Any):
+                    is_causal: Optional[bool] = None, sliding_window: Optional[int] = None, **kwargs: Any):
     causal = bool(getattr(module, "is_causal", False) if is_causal is None else is_causal)
     same_len = query.shape[2] == key.shape[2]
+    # sliding-window layers (Mistral, Qwen2, ...): a query sees the last `sliding_window` keys, itself included
+    window = sliding_window if causal and sliding_window is not None and sliding_window < key.shape[2] else None
     kernel_mask = attention_mask is None or (attention_mask.dtype == torch.uint8 and attention_mask.dim() == 2)
     # grouped-query models (Llama, Mistral, Qwen, ...) hand over the un-repeated [B, Hkv, T, D] key / value
     if same_len and kernel_mask and query.shape[1] % key.shape[1] == 0:
@@ -65,15 +69,21 @@ def _damd_attention(module: nn.Module, query: torch.Tensor, key: torch.Tensor, v
         q, k, v = (t if t.stride(-1) == 1 else t.contiguous() for t in (query, key, value))
         if _supported(q, k, v):
             o = flash_attention(q, k, v, causal=causal, scale=scaling, key_padding=km,
-                                dropout_p=dropout if module.training else 0.0)
+                                dropout_p=dropout if module.training else 0.0, window=window)
             return o.transpose(1, 2), None
     # fallback: SDPA with a boolean [B, 1, 1|Tq, Tk] mask
     mask = attention_mask
+    tq, tk = query.shape[2], key.shape[2]
     if mask is not None and mask.dtype == torch.uint8 and mask.dim() == 2:
-        mask = mask[:, None, None, : key.shape[2]].bool()
+        mask = mask[:, None, None, :tk].bool()
         if causal:  # a decoder batch with padding: SDPA takes one mask, so fold the causal one in
-            tq, tk = query.shape[2], key.shape[2]
             mask = mask & torch.ones(tq, tk, dtype=torch.bool, device=mask.device).tril(tk - tq)
+    if window is not None:  # causal band: keys pos - window + 1 .. pos of the query at position pos = tk - tq + i
+        band = torch.ones(tq, tk, dtype=torch.bool, device=query.device).tril(tk - tq).triu(tk - tq - window + 1)
+        if mask is None:
+            mask = band
+        else:
+            mask = mask & band if mask.dtype == torch.bool else mask.masked_fill(~band, float("-inf"))
     o =torch.nn.functional.scaled_dot_product_attention(query, key, value, attn_mask=mask,
                                                          dropout_p=dropout if module.training else 0.0,
                                                          is_causal=causal and mask is None, scale=scaling,
