@@ -201,6 +201,12 @@ extern "C" void damd_bias_grad_launch(const void*, int64_t, int, int, float*, vo
 extern "C" void damd_gelu_fwd_launch(const void*, void*, int64_t, int, hipStream_t);
 extern "C" void damd_gelu_bwd_bias_launch(const void*, const void*, void*, int64_t, int, int, float*, int, hipStream_t);
 extern "C" void damd_debug_launch(float*, int, int, hipStream_t);
+// launchers (decoder.hip)
+extern "C" void damd_rope_qk_launch(const void*, const void*, void*, void*, const void*, const void*, const int64_t*,
+                                    int, int, int, int, int, int, int, hipStream_t);
+extern "C" void damd_swiglu_fwd_launch(const void*, const void*, void*, int64_t, int, int64_t, int64_t, hipStream_t);
+extern "C" void damd_swiglu_bwd_launch(const void*, const void*, const void*, void*, void*, int64_t, int, int64_t,
+                                       int64_t, hipStream_t);
 
 // common.h: every DAMD_LAUNCH / DAMD_CHECK failure in the device TUs ends here and becomes a
 // c10::Error (Python RuntimeError) naming the launcher and source line.
@@ -1801,6 +1807,92 @@ std::vector<at::Tensor> gelu_bwd_bias(const at::Tensor& dg, const at::Tensor& h,
   return {dh, db};
 }
 
+// ---------------------------------------------------------------- decoder.hip: rotary embedding, SwiGLU
+bool aligned16(const at::Tensor& t) { return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0; }
+
+// cos / sin table of a rotary embedding: [Bc, T, D] with Bc in {1, B}, fp32 or bf16, contiguous D,
+// 16-byte aligned rows
+bool rope_table_ok(const at::Tensor& c, const at::Tensor& q) {
+  if (!c.is_cuda() || c.device() != q.device() || c.dim() != 3) return false;
+  if (c.scalar_type() != at::kFloat && c.scalar_type() != at::kBFloat16) return false;
+  if ((c.size(0) != 1 && c.size(0) != q.size(0)) || c.size(1) != q.size(2) || c.size(2) != q.size(3)) return false;
+  const int64_t vec = 16 / static_cast<int64_t>(c.element_size());
+  // a shared table's batch stride is never used (rope_qk passes 0 for it)
+  return c.stride(2) == 1 && (c.size(0) == 1 || c.stride(0) % vec == 0) && c.stride(1) % vec == 0 && aligned16(c);
+}
+
+// q [B,H,T,D], k [B,Hkv,T,D]: the attention kernels' layout rule (bf16, D in {64,128}, contiguous D,
+// 16-byte aligned strides), H % Hkv == 0; cos, sin [Bc,T,D] of one dtype
+bool rope_supported(const at::Tensor& q, const at::Tensor& k, const at::Tensor& cos, const at::Tensor& sin) {
+  if (!attn_supported(q) || !attn_supported(k) || k.device() != q.device()) return false;
+  if (k.size(0) != q.size(0) || k.size(2) != q.size(2) || k.size(3) != q.size(3)) return false;
+  if (k.size(1) <= 0 || q.size(1) % k.size(1) != 0) return false;
+  if (q.size(0) * q.size(2) > INT32_MAX / 4) return false;  // one workgroup per four tokens
+  return rope_table_ok(cos, q) && rope_table_ok(sin, q) && cos.scalar_type() == sin.scalar_type() &&
+         cos.size(0) == sin.size(0);
+}
+
+// (q_rot, k_rot) = rotary(q, k) -- or, with `backward`, the gradients (dq, dk) of the upstream
+// gradients passed as q, k.  Outputs are [B,H,T,D] views of fresh [B,T,H,D] memory.
+std::vector<at::Tensor> rope_qk(const at::Tensor& q, const at::Tensor& k, const at::Tensor& cos, const at::Tensor& sin,
+                                bool backward) {
+  TORCH_CHECK(attn_supported(q) && attn_supported(k), "rope_qk: q / k need bf16 [B,H,T,D] GPU tensors, D in {64,128}, "
+              "contiguous D, 16-byte aligned strides");
+  TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2) && k.size(3) == q.size(3) && k.size(1) > 0 &&
+                  q.size(1) % k.size(1) == 0,
+              "rope_qk: k must be [B, Hkv, T, D] with q's B, T, D and Hkv dividing q's ", q.size(1), " heads");
+  TORCH_CHECK(rope_table_ok(cos, q) && rope_table_ok(sin, q),
+              "rope_qk: cos / sin must be fp32 or bf16 [Bc, T, D] GPU tensors with Bc in {1, B}, q's T and D, "
+              "contiguous D and 16-byte aligned rows");
+  TORCH_CHECK(cos.scalar_type() == sin.scalar_type() && cos.size(0) == sin.size(0),
+              "rope_qk: cos and sin must share dtype and batch size");
+  TORCH_CHECK(rope_supported(q, k, cos, sin), "rope_qk: q and k on different devices, or too many tokens");
+  const int64_t B = q.size(0), H = q.size(1), T = q.size(2), D = q.size(3), Hkv = k.size(1);
+  auto oq = at::empty({B, T, H, D}, q.options());
+  auto ok = at::empty({B, T, Hkv, D}, q.options());
+  const int64_t strides[10] = {q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
+                               cos.size(0) == 1 ? 0 : cos.stride(0), cos.stride(1),
+                               sin.size(0) == 1 ? 0 : sin.stride(0), sin.stride(1)};
+  damd_rope_qk_launch(q.data_ptr(), k.data_ptr(), oq.data_ptr(), ok.data_ptr(), cos.data_ptr(), sin.data_ptr(), strides,
+                      static_cast<int>(B), static_cast<int>(T), static_cast<int>(H), static_cast<int>(Hkv),
+                      static_cast<int>(D), cos.scalar_type() == at::kBFloat16 ? 1 : 0, backward ? 1 : 0, cur_stream());
+  return {oq.permute({0, 2, 1, 3}), ok.permute({0, 2, 1, 3})};
+}
+
+// gate, up: bf16 [M, I] GPU tensors, contiguous columns, I % 8 == 0, 16-byte aligned rows (the two
+// halves of a packed [M, 2I] projection qualify)
+bool swiglu_half_ok(const at::Tensor& t) {
+  return t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.dim() == 2 && t.size(1) % 8 == 0 &&
+         t.size(1) <= INT32_MAX && (t.size(1) == 0 || t.stride(1) == 1) && t.stride(0) % 8 == 0 && aligned16(t);
+}
+
+bool swiglu_supported(const at::Tensor& gate, const at::Tensor& up) {
+  return swiglu_half_ok(gate) && swiglu_half_ok(up) && gate.sizes() == up.sizes() && gate.device() == up.device();
+}
+
+at::Tensor swiglu_fwd(const at::Tensor& gate, const at::Tensor& up) {
+  TORCH_CHECK(swiglu_supported(gate, up), "swiglu_fwd: gate / up need matching bf16 [M, I] GPU tensors with I % 8 == 0, "
+              "contiguous columns and 16-byte aligned rows");
+  auto y = at::empty(gate.sizes(), gate.options());
+  damd_swiglu_fwd_launch(gate.data_ptr(), up.data_ptr(), y.data_ptr(), gate.size(0), static_cast<int>(gate.size(1)),
+                         gate.stride(0), up.stride(0), cur_stream());
+  return y;
+}
+
+// (dgate, dup), contiguous [M, I], from a contiguous dy
+std::vector<at::Tensor> swiglu_bwd(const at::Tensor& dy, const at::Tensor& gate, const at::Tensor& up) {
+  TORCH_CHECK(swiglu_supported(gate, up), "swiglu_bwd: gate / up need matching bf16 [M, I] GPU tensors with I % 8 == 0, "
+              "contiguous columns and 16-byte aligned rows");
+  TORCH_CHECK(dy.is_cuda() && dy.device() == gate.device() && dy.scalar_type() == at::kBFloat16 && dy.is_contiguous() &&
+                  dy.sizes() == gate.sizes() && aligned16(dy),
+              "swiglu_bwd: dy must be a contiguous bf16 GPU tensor of gate's shape");
+  auto dgate = at::empty(gate.sizes(), gate.options());
+  auto dup = at::empty(gate.sizes(), gate.options());
+  damd_swiglu_bwd_launch(dy.data_ptr(), gate.data_ptr(), up.data_ptr(), dgate.data_ptr(), dup.data_ptr(), gate.size(0),
+                         static_cast<int>(gate.size(1)), gate.stride(0), up.stride(0), cur_stream());
+  return {dgate, dup};
+}
+
 }  // namespace
 
 at::Tensor debug_launch(int64_t n, int64_t mode) {
@@ -1828,6 +1920,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gelu_fwd", &gelu_fwd, py::arg("h"), py::arg("exact") = false);
   m.def("debug_launch", &debug_launch, "launch-check probe: mode 0 valid, 1 LDS over the limit, 2 oversized block");
   m.def("gelu_bwd_bias", &gelu_bwd_bias, py::arg("dg"), py::arg("h"), py::arg("bias_dtype"), py::arg("exact") = false);
+  m.def("rope_supported", &rope_supported);
+  m.def("rope_qk", &rope_qk, py::arg("q"), py::arg("k"), py::arg("cos"), py::arg("sin"), py::arg("backward") = false);
+  m.def("swiglu_supported", &swiglu_supported);
+  m.def("swiglu_fwd", &swiglu_fwd);
+  m.def("swiglu_bwd", &swiglu_bwd);
   m.def("attn_supported", &attn_supported);
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("scale"),
         py::arg("kmask") = py::none(), py::arg("drop_p") = 0.0, py::arg("seed") = 0, py::arg("seed_t") = py::none(),

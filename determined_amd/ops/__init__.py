@@ -177,7 +177,7 @@ _DISABLED = frozenset(f.strip() for f in os.environ.get("DAMD_DISABLE_FUSIONS", 
 def fusion_enabled(name: str) -> bool:
     """Model-level fusions can be switched off for A/B measurements with
     ``DAMD_DISABLE_FUSIONS=stem_conv,stem_stats,stem_pool,split_grad,avgpool,igemm_conv,conv_stats,bn_conv,bn_prologue,bn_lazy_bwd,
-    compact_shortcut_grad,bn_residual_fold,weight_cache,phase_bn_epilogue`` (the replacement is the
+    compact_shortcut_grad,bn_residual_fold,weight_cache,phase_bn_epilogue,rope,swiglu`` (the replacement is the
     plain PyTorch / MIOpen composition, never a silent eager fallback of a kernel)."""
     return name not in _DISABLED
 

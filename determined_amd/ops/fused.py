@@ -4,7 +4,8 @@
 straight from the bf16 ``[B, T, Vp]`` LM-head output: no shifted slice, no fp32 copy of the
 logits, one read forward, one read + one write backward (the gradient is written in place
 over the logits, which are dead after the loss).  ``FusedLinear`` is ``nn.Linear`` whose
-bias gradient is a single-pass column sum instead of a generic reduction.
+bias gradient is a single-pass column sum instead of a generic reduction.  ``swiglu(gate, up)`` is
+the Llama-style MLP activation ``silu(gate) * up`` as one kernel each way (``csrc/decoder.hip``).
 """
 
 import os
@@ -239,6 +240,35 @@ def linear_gelu(linear: nn.Linear, x: torch.Tensor, approximate: str = "tanh") -
             and linear.weight.dtype == torch.bfloat16 and x.is_contiguous() and _bf16_compute():
         return _LinearGeluFn.apply(x, linear.weight, linear.bias, approximate == "none")
     return F.gelu(linear(x), approximate=approximate)
+
+
+class _SwiGLUFn(torch.autograd.Function):
+    """``silu(gate) * up`` over ``[M, I]`` bf16 rows (csrc/decoder.hip): one pass forward, one pass
+    backward for both gradients; only ``gate`` and ``up`` are saved (the stock composition also
+    keeps ``silu(gate)``)."""
+
+    @staticmethod
+    def forward(ctx, gate, up):
+        ctx.save_for_backward(gate, up)
+        return _ext().swiglu_fwd(gate, up)
+
+    @staticmethod
+    def backward(ctx, dy):
+        gate, up = ctx.saved_tensors
+        dgate, dup = _ext().swiglu_bwd(dy.contiguous(), gate, up)
+        return dgate, dup
+
+
+def swiglu(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
+    """``F.silu(gate) * up`` (the activation of a Llama-style MLP) for ``[..., I]`` tensors.  bf16 GPU
+    tensors with ``I % 8 == 0`` and 16-byte aligned rows -- the two halves of a packed ``[M, 2I]``
+    gate-up projection included -- run the fused kernels; anything else the plain composition."""
+    if gate.is_cuda and gate.dim() >= 1 and gate.shape == up.shape and gate.numel() > 0:
+        I = gate.shape[-1]
+        g2, u2 = (t if t.dim() == 2 else t.reshape(-1, I) for t in (gate, up))
+        if _ext().swiglu_supported(g2, u2):
+            return _SwiGLUFn.apply(g2, u2).view(gate.shape)
+    return F.silu(gate) * up
 
 
 class FusedLinear(nn.Linear):

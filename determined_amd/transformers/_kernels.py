@@ -11,6 +11,15 @@
   sliding-window layers (``sliding_window=`` from Mistral / Qwen2-style attention) run the kernels'
   band mode (``window=``);
 * ``LlamaRMSNorm`` / ``MistralRMSNorm`` / ``Qwen2RMSNorm`` -> ``FusedRMSNorm`` (``csrc/norm.hip``);
+* ``LlamaAttention`` / ``MistralAttention`` / ``Qwen2Attention`` -> a forward whose rotary embedding of
+  the query and key is ONE ``csrc/decoder.hip`` kernel (``ops.rotary.apply_rotary``: strided
+  projection views in, the attention kernels' ``[B, T, H, D]`` memory out; the backward is one launch
+  for dQ and dK); a KV cache (the one HF creates by default, ``use_cache=True``, included) is updated
+  with the rotated key as in the stock forward; extra sub-modules (q / k norms) take the original forward;
+* gated MLPs (``gate_proj`` / ``up_proj`` / ``down_proj`` with a SiLU ``act_fn``) ->
+  ``down_proj(ops.fused.swiglu(gate, up))``: one ``csrc/decoder.hip`` kernel each way, two saved
+  ``[tokens, intermediate]`` activations instead of three (other activations keep their forward);
+  ``DAMD_DISABLE_FUSIONS=rope,swiglu`` leaves the stock forwards in place;
 * ``BertSelfOutput`` / ``BertOutput`` (dense -> dropout -> LayerNorm(. + residual)) -> the dense GEMM
   followed by ONE ``csrc/norm.hip`` kernel doing residual add + dropout + LayerNorm (its backward
   emits both gradients in one pass);
@@ -141,6 +150,56 @@ def _fused_self_attention_forward(self, hidden_states: torch.Tensor, attention_m
     return o.transpose(1, 2).reshape(B, T, H * D), None
 
 
+def _swiglu_mlp_forward(self, x: torch.Tensor) -> torch.Tensor:
+    from determined_amd.ops.fused import swiglu
+
+    return self.down_proj(swiglu(self.gate_proj(x), self.up_proj(x)))
+
+
+_ROPE_ATTENTIONS = ("LlamaAttention", "MistralAttention", "Qwen2Attention")
+_ROPE_ATTENTION_CHILDREN = {"q_proj", "k_proj", "v_proj", "o_proj"}
+
+
+def _rope_attention_forward(self, hidden_states: torch.Tensor, position_embeddings: Any = None,
+                            attention_mask: Optional[torch.Tensor] = None, past_key_values: Any = None,
+                            **kwargs: Any):
+    """``LlamaAttention.forward`` (and its Mistral / Qwen2 twins) with the rotary embedding of the
+    query and key as ONE kernel (``ops.rotary.apply_rotary``), whose ``[B, T, H, D]``-memory outputs
+    go straight to the registered attention interface.  A KV cache is updated with the rotated key and
+    the value as in the stock forward (HF's model forward creates one per call unless
+    ``use_cache=False``, in training too; its ``update`` copies both, so training steps are better run
+    with ``use_cache=False``).  A module with children this forward does not know (q / k norms, ...)
+    takes the original forward."""
+    import sys
+
+    from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
+
+    from determined_amd.ops.rotary import apply_rotary
+
+    if position_embeddings is None or set(self._modules) != _ROPE_ATTENTION_CHILDREN:
+        return self._damd_orig_forward(hidden_states, position_embeddings, attention_mask, past_key_values, **kwargs)
+    input_shape = hidden_states.shape[:-1]
+    hidden_shape = (*input_shape, -1, self.head_dim)
+    query = self.q_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+    key = self.k_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+    value = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)
+    cos, sin = position_embeddings
+    query, key = apply_rotary(query, key, cos, sin)
+    if past_key_values is not None:
+        key, value = past_key_values.update(key, value, self.layer_idx)
+    cls = type(self).__name__
+    if cls == "MistralAttention":
+        kwargs["sliding_window"] = getattr(self.config, "sliding_window", None)
+    elif cls == "Qwen2Attention":
+        kwargs["sliding_window"] = self.sliding_window
+    attention = ALL_ATTENTION_FUNCTIONS.get_interface(self.config._attn_implementation,
+                                                      sys.modules[type(self).__module__].eager_attention_forward)
+    out, weights = attention(self, query, key, value, attention_mask,
+                             dropout=0.0 if not self.training else self.attention_dropout, scaling=self.scaling,
+                             **kwargs)
+    return self.o_proj(out.reshape(*input_shape, -1).contiguous()), weights
+
+
 def _to_fused(ln: nn.LayerNorm) -> FusedLayerNorm:
     f = FusedLayerNorm(ln.normalized_shape, eps=ln.eps, bias=ln.bias is not None,
                        device=ln.weight.device, dtype=ln.weight.dtype)
@@ -203,6 +262,16 @@ def accelerate(model: nn.Module, sparse_mlm_head: bool = False) -> nn.Module:
                     "_damd_orig_forward" not in mod.__dict__:
                 mod._damd_orig_forward = mod.forward
                 mod.forward = types.MethodType(_fused_self_attention_forward, mod)
+    from determined_amd.ops import fusion_enabled
+
+    for mod in model.modules():  # Llama-style decoder layers: SwiGLU and rotary embedding as one kernel each
+        cls = type(mod).__name__
+        if fusion_enabled("swiglu") and type(getattr(mod, "act_fn", None)).__name__ in ("SiLU", "SiLUActivation") and \
+                all(isinstance(getattr(mod, n, None), nn.Linear) for n in ("gate_proj", "up_proj", "down_proj")):
+            mod.forward = types.MethodType(_swiglu_mlp_forward, mod)
+        elif fusion_enabled("rope") and cls in _ROPE_ATTENTIONS and "_damd_orig_forward" not in mod.__dict__:
+            mod._damd_orig_forward = mod.forward
+            mod.forward = types.MethodType(_rope_attention_forward, mod)
     for mod in model.modules():  # the bias gradient as one kernel (bf16 weights, no / bf16 autocast)
         if type(mod) is nn.Linear and mod.bias is not None and mod.out_features % 2 == 0:
             if "_damd_dense_forward" in mod.__dict__:  # a sparse MLM decoder from an earlier call: keep its wrapper

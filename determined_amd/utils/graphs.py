@@ -101,7 +101,12 @@ class GraphedStep:
 
     ``optimizers``: fused optimizers whose hyperparameters are refreshed on the device before every
     replay.  ``restore``: modules / optimizers whose state is rolled back after the warm-up runs, so
-    the warm-up does not train (the first call then performs exactly one update: the first replay)."""
+    the warm-up does not train (the first call then performs exactly one update: the first replay).
+
+    A model that already ran an eager backward on another stream must not still hold that step's
+    autograd graph when it is captured (keep ``.detach()``-ed outputs of eager steps, or capture first):
+    the live graph keeps the parameters' gradient accumulators on the stream of the eager run, and a
+    capture whose backward accumulates there fails."""
 
     def __init__(self, fn: Callable[[], Any], warmup: int = 3, pool: Optional[Any] = None,
                  optimizers: Sequence[Any] = (), restore: Sequence[Any] = (),
