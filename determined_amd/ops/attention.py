@@ -17,6 +17,14 @@ range whose bounds do not decrease with ``q``.  ``band_ranges`` builds the four 
 describe it on the device, and the kernels' third mask mode visits only the key tiles / query blocks
 inside the band: O(T * W) work, no mask tensor, composable with ``key_padding`` and dropout.
 
+Generation against a KV cache (``cached_attention``): a query chunk of ``Tq`` rows at the END of ``Tk
+>= Tq`` keys (query row ``i`` at position ``Tk - Tq + i``), forward only.  The flash-decoding kernels
+in ``csrc/attention_decode.hip`` pack the ``H / Hkv`` heads of a K/V head times the ``Tq`` rows into
+the MFMA columns (at most 32 packed rows: one decode token for groups up to 32, short speculative
+chunks), split the keys over the chip and combine fp32 partials; causal, ``window=`` and
+``key_padding`` (left-padded batches) masks.  Longer chunks (chunked prefill) and calls that need a
+gradient use SDPA with the equivalent dense mask (``cached_mask``).
+
 Anything else (CPU tensors, fp32, other head sizes) uses PyTorch's ``scaled_dot_product_attention``
 -- on ROCm with the composable-kernel backend preferred.
 """
@@ -310,3 +318,57 @@ def qkv_attention(qkv: torch.Tensor, causal: bool = True, dropout_p: float = 0.0
         mask = key_padding[:, None, None, :T].bool()
     return F.scaled_dot_product_attention(q, k, v, attn_mask=mask, dropout_p=dropout_p,
                                           is_causal=causal and mask is None, scale=scale)
+
+
+def cached_mask(tq: int, tk: int, causal: bool, window: Optional[int] = None,
+                key_padding: Optional[torch.Tensor] = None, device=None) -> Optional[torch.Tensor]:
+    """The dense boolean mask (True = attend; ``[Tq, Tk]`` or ``[B, 1, Tq, Tk]``) of ``Tq`` queries at
+    the end of ``Tk`` keys, or None when every key is attended.  The query in row ``i`` sits at position
+    ``p = tk - tq + i``: ``causal`` keeps the keys ``<= p``, ``window`` (with ``causal``) the keys ``>= p -
+    window + 1``, ``key_padding [B, >= Tk]`` (nonzero = valid) the valid keys."""
+    mask = None
+    if causal:
+        mask = torch.ones(tq, tk, dtype=torch.bool, device=device).tril(tk - tq)
+        if window is not None:
+            mask = mask.triu(tk - tq - window + 1)
+    if key_padding is not None:
+        kp = key_padding[:, None, None, :tk].bool()
+        mask = kp if mask is None else mask & kp
+    return mask
+
+
+def _decode_fwd(q, k, v, causal: bool, scale: float, km, window: int):
+    """The flash-decoding kernels (``csrc/attention_decode.hip``): ``(o, lse)``."""
+    return _ext().attn_decode_fwd(q, k, v, causal, scale, km, window)
+
+
+def cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
+                     scale: Optional[float] = None, key_padding: Optional[torch.Tensor] = None,
+                     window: Optional[int] = None) -> torch.Tensor:
+    """Attention of a query chunk ``q [B, H, Tq, D]`` at the end of the keys / values ``[B, Hkv, Tk, D]``
+    of a KV cache (``Tq <= Tk``, ``H % Hkv == 0``; query row ``i`` at position ``Tk - Tq + i``).  ``causal``:
+    keys up to the query's position; ``window`` (needs ``causal``): only its last ``window`` keys;
+    ``key_padding``: a ``key_mask`` tensor or a ``[B, Tk]`` validity mask.  Returns ``[B, H, Tq, D]`` (from
+    the kernels: in ``[B, Tq, H, D]`` memory).
+
+    bf16 GPU tensors with ``D`` in {64, 128} and ``(H / Hkv) * Tq <= 32`` run the flash-decoding kernels
+    when no gradient is needed (grad mode off, or none of q / k / v requires one): a query with no
+    attendable key gives zeros.  Everything else goes through SDPA with ``cached_mask``."""
+    if window is not None and not causal:
+        raise ValueError("window= needs causal=True")
+    if window is not None and window < 1:
+        raise ValueError("window must be >= 1")
+    tq, tk = q.shape[2], k.shape[2]
+    if tq > tk:
+        raise ValueError(f"cached_attention: {tq} queries against {tk} keys (the queries are the last keys)")
+    scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else float(scale)
+    needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))
+    if q.is_cuda and not needs_grad and _ext().attn_decode_supported(q, k, v):
+        km = key_padding
+        if km is not None and (km.dtype != torch.uint8 or km.shape[1] % 64 or km.shape[1] < tk):
+            km = key_mask(km[:, :tk])
+        return _decode_fwd(q, k, v, causal, scale, km, 0 if window is None else window)[0]
+    if q.is_cuda:
+        _configure()
+    mask = cached_mask(tq, tk, causal, window, key_padding, q.device)
+    return F.scaled_dot_product_attention(q, k, v, attn_mask=mask, scale=scale, enable_gqa=k.shape[1] != q.shape[1])

@@ -28,8 +28,14 @@
   ``ops.fused.FusedLinear``'s forward: its bias gradient is one single-pass column-sum kernel
   (``csrc/fused.hip`` bias_grad) instead of a generic torch reduction per layer.
 
-Shapes the kernels do not serve (CPU, fp32, head dim not in {64, 128}, cross attention with
-different lengths) fall back to PyTorch SDPA with the equivalent boolean mask.  Reference: the
+A query shorter than the keys (the decode steps of ``generate()`` against the KV cache, the new
+tokens being the last keys) goes to ``ops.attention.cached_attention``: the flash-decoding kernels of
+``csrc/attention_decode.hip`` for up to 32 packed rows ``(H / Hkv) * Tq`` -- causal, sliding window and
+the key mask of a left-padded batch included -- and SDPA with the same bottom-right aligned mask for
+longer chunks or when a gradient is needed.
+
+Shapes the kernels do not serve (CPU, fp32, head dim not in {64, 128}) fall back to PyTorch SDPA
+with the equivalent boolean mask.  Reference: the
 HF Trainer path of ``harness/determined/transformers/_hf_callback.py`` runs the stock modules.
 """
 
@@ -40,7 +46,7 @@ from typing import Any, Optional
 import torch
 from torch import nn
 
-from determined_amd.ops.attention import _supported, flash_attention, key_mask
+from determined_amd.ops.attention import _supported, cached_attention, cached_mask, flash_attention, key_mask
 from determined_amd.ops.norm import FusedLayerNorm, FusedRMSNorm, residual_dropout_layer_norm
 
 NAME = "damd"
@@ -80,15 +86,19 @@ def _damd_attention(module: nn.Module, query: torch.Tensor, key: torch.Tensor, v
             o = flash_attention(q, k, v, causal=causal, scale=scaling, key_padding=km,
                                 dropout_p=dropout if module.training else 0.0, window=window)
             return o.transpose(1, 2), None
+    tq, tk = query.shape[2], key.shape[2]
+    # a query chunk at the end of a KV cache (generation): the flash-decoding kernels, or SDPA with the same mask
+    if tq < tk and kernel_mask and query.shape[1] % key.shape[1] == 0 and not (module.training and dropout > 0):
+        q, k, v = (t if t.stride(-1) == 1 else t.contiguous() for t in (query, key, value))
+        o = cached_attention(q, k, v, causal=causal, scale=scaling, key_padding=attention_mask, window=window)
+        return o.transpose(1, 2).contiguous(), None
     # fallback: SDPA with a boolean [B, 1, 1|Tq, Tk] mask
     mask = attention_mask
-    tq, tk = query.shape[2], key.shape[2]
     if mask is not None and mask.dtype == torch.uint8 and mask.dim() == 2:
-        mask = mask[:, None, None, :tk].bool()
-        if causal:  # a decoder batch with padding: SDPA takes one mask, so fold the causal one in
-            mask = mask & torch.ones(tq, tk, dtype=torch.bool, device=mask.device).tril(tk - tq)
-    if window is not None:  # causal band: keys pos - window + 1 .. pos of the query at position pos = tk - tq + i
-        band = torch.ones(tq, tk, dtype=torch.bool, device=query.device).tril(tk - tq).triu(tk - tq - window + 1)
+        # a decoder batch with padding: SDPA takes one mask, so the causal one (and the window) is folded in
+        mask = cached_mask(tq, tk, causal, window, mask, query.device)
+    elif window is not None:  # causal band: keys pos - window + 1 .. pos of the query at position pos = tk - tq + i
+        band = cached_mask(tq, tk, True, window, None, query.device)
         if mask is None:
             mask = band
         else:
