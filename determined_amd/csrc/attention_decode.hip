@@ -365,6 +365,15 @@ int damd_attn_decode_split(int B, int Hkv, int Tq, int Tk, int window) {
   return S < 1 ? 1 : static_cast<int>(S);
 }
 
+// The combine step on its own (attention_chunk.hip writes the same partials): po / pml as the kernels
+// above leave them for `split` key splits, so: o's (b, h, t) strides in elements.
+void damd_attn_decode_combine_launch(const float* po, const float* pml, int split, void* o, const int64_t* so,
+                                     float* lse, int B, int H, int Tq, int D, hipStream_t st) {
+  const int64_t rows = static_cast<int64_t>(B) * H * Tq, threads = rows * (D / 4);
+  DAMD_LAUNCH(attn_decode_combine_kernel, dim3(static_cast<unsigned>((threads + 255) / 256)), dim3(256), 0, st, po,
+              pml, split, static_cast<bf16_t*>(o), Strides{so[0], so[1], so[2]}, lse, H, Tq, D, rows);
+}
+
 // strides: 4 tensors (q, k, v, o) x (b, h, t) in elements; km: optional [B][kms] key mask with
 // kms >= pad64(Tk).  k, v have Hkv heads, H % Hkv == 0, (H / Hkv) * Tq <= 32, 1 <= Tq <= Tk (checked
 // by the binding).  split > 1: po holds split * B * H * Tq * D floats, pml 2 * split * B * H * Tq.
@@ -390,11 +399,7 @@ void damd_attn_decode_launch(const void* q, const void* k, const void* v, void* 
     if (two) DAMD_LAUNCH((attn_decode_kernel<128, 2>), grid, dim3(kThreads), 0, st, a);
     else DAMD_LAUNCH((attn_decode_kernel<128, 1>), grid, dim3(kThreads), 0, st, a);
   }
-  if (split > 1) {
-    const int64_t rows = static_cast<int64_t>(B) * H * Tq, threads = rows * (D / 4);
-    DAMD_LAUNCH(attn_decode_combine_kernel, dim3(static_cast<unsigned>((threads + 255) / 256)), dim3(256), 0, st, po,
-                pml, split, a.o, a.so, lse, H, Tq, D, rows);
-  }
+  if (split > 1) damd_attn_decode_combine_launch(po, pml, split, o, strides + 9, lse, B, H, Tq, D, st);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
-// MFMA fragment helpers shared by the attention kernels (attention.hip, attention_decode.hip):
-// the vector types, the 16x16x32 bf16 MFMA, hardware bf16 conversion, the cross-row reductions of
-// the S^T layout and the transposed LDS reads.  The fragment layout is described at the top of
+// MFMA fragment helpers shared by the attention kernels (attention.hip, attention_decode.hip,
+// attention_chunk.hip): the vector types, the 16x16x32 bf16 MFMA, hardware bf16 conversion, the
+// cross-row reductions of the S^T layout and the transposed LDS reads.  The fragment layout is described at the top of
 // attention.hip.
 #pragma once
 

@@ -195,6 +195,11 @@ extern "C" int damd_attn_decode_split(int, int, int, int, int);
 extern "C" void damd_attn_decode_launch(const void*, const void*, const void*, void*, float*, float*, float*,
                                         const int64_t*, int, int, int, int, int, int, float, int, int, const uint8_t*,
                                         int64_t, int, hipStream_t);
+// launchers (attention_chunk.hip)
+extern "C" int damd_attn_chunk_plan(int, int, int, int, int, int, int, int*);
+extern "C" void damd_attn_chunk_launch(const void*, const void*, const void*, void*, float*, float*, float*,
+                                       const int64_t*, int, int, int, int, int, int, float, int, int, const uint8_t*,
+                                       int64_t, int, int, hipStream_t);
 // launchers (fused.hip)
 extern "C" void damd_lm_ce_fwd_launch(const void*, const int64_t*, int64_t, int, int, int, int64_t, float*, float*,
                                       hipStream_t);
@@ -1623,6 +1628,23 @@ bool attn_decode_supported(const at::Tensor& q, const at::Tensor& k, const at::T
   return Tq >= 1 && Tq <= Tk && (H / Hkv) * Tq <= 32 && B * Hkv <= 65535 && Tk < (int64_t{1} << 30);
 }
 
+// The optional key mask of a cached-attention call (decode and chunk kernels): uint8 [B, >= pad64(Tk)]
+// on q's device; returns its data (nullptr: none) and the row stride.
+static const uint8_t* cache_key_mask(const c10::optional<at::Tensor>& kmask, const at::Tensor& q, int64_t Tk,
+                                     int64_t* kms) {
+  if (!kmask.has_value() || !kmask->defined()) return nullptr;
+  const at::Tensor& m = *kmask;
+  TORCH_CHECK(m.is_cuda() && m.scalar_type() == at::kByte && m.dim() == 2 && m.stride(1) == 1 &&
+                  m.device() == q.device(),
+              "key mask: uint8 [B, Tpad] with contiguous rows on q's device");
+  TORCH_CHECK(m.size(0) == q.size(0) && m.size(1) >= (Tk + 63) / 64 * 64,
+              "key mask: [B, Tpad] with Tpad >= Tk rounded up to a multiple of 64");
+  TORCH_CHECK(m.stride(0) % 4 == 0 && (reinterpret_cast<uintptr_t>(m.data_ptr()) & 3) == 0,
+              "key mask: rows must be 4-byte aligned");
+  *kms = m.stride(0);
+  return m.data_ptr<uint8_t>();
+}
+
 // The key split a call with these tensors uses (DAMD_ATTN_DECODE_SPLIT or the launcher's rule).
 int64_t attn_decode_split(const at::Tensor& q, const at::Tensor& k, int64_t window) {
   return damd_attn_decode_split(static_cast<int>(q.size(0)), static_cast<int>(k.size(1)), static_cast<int>(q.size(2)),
@@ -1648,19 +1670,7 @@ std::vector<at::Tensor> attn_decode_fwd(const at::Tensor& q, const at::Tensor& k
   TORCH_CHECK(window >= 0 && (window == 0 || causal), "attn_decode_fwd: window >= 0, and window > 0 needs causal");
   TORCH_CHECK(split >= 0 && split <= 256, "attn_decode_fwd: split in [0, 256]");
   int64_t kms = 0;
-  const uint8_t* km = nullptr;
-  if (kmask.has_value() && kmask->defined()) {
-    const at::Tensor& m = *kmask;
-    TORCH_CHECK(m.is_cuda() && m.scalar_type() == at::kByte && m.dim() == 2 && m.stride(1) == 1 &&
-                    m.device() == q.device(),
-                "key mask: uint8 [B, Tpad] with contiguous rows on q's device");
-    TORCH_CHECK(m.size(0) == B && m.size(1) >= (Tk + 63) / 64 * 64,
-                "key mask: [B, Tpad] with Tpad >= Tk rounded up to a multiple of 64");
-    TORCH_CHECK(m.stride(0) % 4 == 0 && (reinterpret_cast<uintptr_t>(m.data_ptr()) & 3) == 0,
-                "key mask: rows must be 4-byte aligned");
-    kms = m.stride(0);
-    km = m.data_ptr<uint8_t>();
-  }
+  const uint8_t* km = cache_key_mask(kmask, q, Tk, &kms);
   const int64_t W = window < Tk ? window : 0;  // a window that holds every key is no window
   const int S = split > 0 ? static_cast<int>(split) : static_cast<int>(attn_decode_split(q, k, W));
   auto o = at::empty({B, Tq, H, D}, q.options()).permute({0, 2, 1, 3});
@@ -1681,6 +1691,64 @@ std::vector<at::Tensor> attn_decode_fwd(const at::Tensor& q, const at::Tensor& k
                             static_cast<int>(B), static_cast<int>(H), static_cast<int>(Hkv), static_cast<int>(Tq),
                             static_cast<int>(Tk), static_cast<int>(D), static_cast<float>(scale), causal ? 1 : 0,
                             static_cast<int>(W), km, kms, S, cur_stream());
+  return {o, lse};
+}
+
+// ---------------------------------------------------------------- chunked-prefill attention (KV cache)
+// The same tensors and masks as the decode kernels with more than 32 packed rows (attention_chunk.hip):
+// no cap on (H / Hkv) * Tq beyond 32-bit row indices.
+bool attn_chunk_supported(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
+  if (!attn_supported(q) || !attn_supported(k) || !attn_supported(v)) return false;
+  if (k.device() != q.device() || v.device() != q.device() || v.sizes() != k.sizes()) return false;
+  const int64_t B = q.size(0), H = q.size(1), Tq = q.size(2), Hkv = k.size(1), Tk = k.size(2);
+  if (k.size(0) != B || k.size(3) != q.size(3) || Hkv < 1 || H % Hkv != 0) return false;
+  return Tq >= 1 && Tq <= Tk && (H / Hkv) * Tq < (int64_t{1} << 30) && B * Hkv <= 65535 && Tk < (int64_t{1} << 30);
+}
+
+// split: 0 = the launcher's rule (damd_attn_chunk_plan), else that many workgroups per (query block,
+// batch, kv head).
+std::vector<at::Tensor> attn_chunk_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, bool causal,
+                                       double scale, const c10::optional<at::Tensor>& kmask, int64_t window,
+                                       int64_t split) {
+  TORCH_CHECK(attn_supported(q) && attn_supported(k) && attn_supported(v),
+              "attn_chunk_fwd: unsupported layout (need bf16 [B,H,T,D] GPU tensors, D in {64,128}, contiguous D, "
+              "16-byte aligned strides)");
+  TORCH_CHECK(k.device() == q.device() && v.device() == q.device(), "attn_chunk_fwd: tensors on different devices");
+  const int64_t B = q.size(0), H = q.size(1), Tq = q.size(2), D = q.size(3), Hkv = k.size(1), Tk = k.size(2);
+  TORCH_CHECK(k.size(0) == B && k.size(3) == D && Hkv > 0 && H % Hkv == 0,
+              "k shape mismatch: need [B, Hkv, Tk, D] with q's B, D and Hkv dividing q's ", H, " heads");
+  TORCH_CHECK(v.sizes() == k.sizes(), "v shape mismatch");
+  TORCH_CHECK(Tq >= 1 && Tq <= Tk, "attn_chunk_fwd: need 1 <= Tq <= Tk (got Tq = ", Tq, ", Tk = ", Tk, ")");
+  TORCH_CHECK(B * Hkv <= 65535 && Tk < (int64_t{1} << 30) && (H / Hkv) * Tq < (int64_t{1} << 30),
+              "attn_chunk_fwd: B * Hkv, Tk or (H / Hkv) * Tq too large");
+  TORCH_CHECK(window >= 0 && (window == 0 || causal), "attn_chunk_fwd: window >= 0, and window > 0 needs causal");
+  TORCH_CHECK(split >= 0 && split <= 256, "attn_chunk_fwd: split in [0, 256]");
+  int64_t kms = 0;
+  const uint8_t* km = cache_key_mask(kmask, q, Tk, &kms);
+  const int64_t W = window < Tk ? window : 0;  // a window that holds every key is no window
+  auto o = at::empty({B, Tq, H, D}, q.options()).permute({0, 2, 1, 3});
+  auto lse = at::empty({B, H, Tq}, q.options().dtype(at::kFloat));
+  if (B == 0) return {o, lse};
+  int qt = 1;
+  const int rule = damd_attn_chunk_plan(static_cast<int>(B), static_cast<int>(Hkv), static_cast<int>(H / Hkv),
+                                        static_cast<int>(Tq), static_cast<int>(Tk), static_cast<int>(D),
+                                        static_cast<int>(W), &qt);
+  const int S = split > 0 ? static_cast<int>(split) : rule;
+  at::Tensor po, pml;  // from the caching allocator per call: capture-safe, no global buffer
+  if (S > 1) {
+    po = at::empty({S, B, H, Tq, D}, lse.options());
+    pml = at::empty({2, S, B, H, Tq}, lse.options());
+  }
+  std::vector<int64_t> s;
+  push_strides(s, q);
+  push_strides(s, k);
+  push_strides(s, v);
+  push_strides(s, o);
+  damd_attn_chunk_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(),
+                         S > 1 ? po.data_ptr<float>() : nullptr, S > 1 ? pml.data_ptr<float>() : nullptr, s.data(),
+                         static_cast<int>(B), static_cast<int>(H), static_cast<int>(Hkv), static_cast<int>(Tq),
+                         static_cast<int>(Tk), static_cast<int>(D), static_cast<float>(scale), causal ? 1 : 0,
+                         static_cast<int>(W), km, kms, S, qt, cur_stream());
   return {o, lse};
 }
 
@@ -2013,6 +2081,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_decode_supported", &attn_decode_supported);
   m.def("attn_decode_split", &attn_decode_split, py::arg("q"), py::arg("k"), py::arg("window") = 0);
   m.def("attn_decode_fwd", &attn_decode_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
+        py::arg("scale"), py::arg("kmask") = py::none(), py::arg("window") = 0, py::arg("split") = 0);
+  m.def("attn_chunk_supported", &attn_chunk_supported);
+  m.def("attn_chunk_fwd", &attn_chunk_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
         py::arg("scale"), py::arg("kmask") = py::none(), py::arg("window") = 0, py::arg("split") = 0);
   m.def("bn_supported", &bn_supported);
   m.def("bn_act_fwd", &bn_act_fwd);

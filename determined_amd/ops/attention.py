@@ -22,8 +22,10 @@ Generation against a KV cache (``cached_attention``): a query chunk of ``Tq`` ro
 in ``csrc/attention_decode.hip`` pack the ``H / Hkv`` heads of a K/V head times the ``Tq`` rows into
 the MFMA columns (at most 32 packed rows: one decode token for groups up to 32, short speculative
 chunks), split the keys over the chip and combine fp32 partials; causal, ``window=`` and
-``key_padding`` (left-padded batches) masks.  Longer chunks (chunked prefill) and calls that need a
-gradient use SDPA with the equivalent dense mask (``cached_mask``).
+``key_padding`` (left-padded batches) masks.  Longer chunks (chunked prefill, the next turn of a chat
+against a kept cache) run the query-major kernel in ``csrc/attention_chunk.hip``: the packed rows in
+position-major order, K/V tiles staged once per workgroup for every head of the group, the same masks
+and key split.  Calls that need a gradient use SDPA with the equivalent dense mask (``cached_mask``).
 
 Anything else (CPU tensors, fp32, other head sizes) uses PyTorch's ``scaled_dot_product_attention``
 -- on ROCm with the composable-kernel backend preferred.
@@ -342,6 +344,11 @@ def _decode_fwd(q, k, v, causal: bool, scale: float, km, window: int):
     return _ext().attn_decode_fwd(q, k, v, causal, scale, km, window)
 
 
+def _chunk_fwd(q, k, v, causal: bool, scale: float, km, window: int):
+    """The chunked-prefill kernel (``csrc/attention_chunk.hip``): ``(o, lse)``."""
+    return _ext().attn_chunk_fwd(q, k, v, causal, scale, km, window)
+
+
 def cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
                      scale: Optional[float] = None, key_padding: Optional[torch.Tensor] = None,
                      window: Optional[int] = None) -> torch.Tensor:
@@ -351,9 +358,10 @@ def cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: 
     ``key_padding``: a ``key_mask`` tensor or a ``[B, Tk]`` validity mask.  Returns ``[B, H, Tq, D]`` (from
     the kernels: in ``[B, Tq, H, D]`` memory).
 
-    bf16 GPU tensors with ``D`` in {64, 128} and ``(H / Hkv) * Tq <= 32`` run the flash-decoding kernels
-    when no gradient is needed (grad mode off, or none of q / k / v requires one): a query with no
-    attendable key gives zeros.  Everything else goes through SDPA with ``cached_mask``."""
+    bf16 GPU tensors with ``D`` in {64, 128} run the HIP kernels when no gradient is needed (grad mode
+    off, or none of q / k / v requires one): the flash-decoding kernels up to ``(H / Hkv) * Tq = 32``
+    packed rows, the chunked-prefill kernel above; a query with no attendable key gives zeros.
+    Everything else goes through SDPA with ``cached_mask``."""
     if window is not None and not causal:
         raise ValueError("window= needs causal=True")
     if window is not None and window < 1:
@@ -363,11 +371,12 @@ def cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: 
         raise ValueError(f"cached_attention: {tq} queries against {tk} keys (the queries are the last keys)")
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else float(scale)
     needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))
-    if q.is_cuda and not needs_grad and _ext().attn_decode_supported(q, k, v):
+    if q.is_cuda and not needs_grad and _ext().attn_chunk_supported(q, k, v):
         km = key_padding
         if km is not None and (km.dtype != torch.uint8 or km.shape[1] % 64 or km.shape[1] < tk):
             km = key_mask(km[:, :tk])
-        return _decode_fwd(q, k, v, causal, scale, km, 0 if window is None else window)[0]
+        fwd = _chunk_fwd if (q.shape[1] // k.shape[1]) * tq > 32 else _decode_fwd
+        return fwd(q, k, v, causal, scale, km, 0 if window is None else window)[0]
     if q.is_cuda:
         _configure()
     mask = cached_mask(tq, tk, causal, window, key_padding, q.device)

@@ -31,8 +31,9 @@
 A query shorter than the keys (the decode steps of ``generate()`` against the KV cache, the new
 tokens being the last keys) goes to ``ops.attention.cached_attention``: the flash-decoding kernels of
 ``csrc/attention_decode.hip`` for up to 32 packed rows ``(H / Hkv) * Tq`` -- causal, sliding window and
-the key mask of a left-padded batch included -- and SDPA with the same bottom-right aligned mask for
-longer chunks or when a gradient is needed.
+the key mask of a left-padded batch included --, the chunked-prefill kernel of
+``csrc/attention_chunk.hip`` for longer chunks (a new turn against a kept cache), and SDPA with the same
+bottom-right aligned mask when a gradient is needed.
 
 Shapes the kernels do not serve (CPU, fp32, head dim not in {64, 128}) fall back to PyTorch SDPA
 with the equivalent boolean mask.  Reference: the
