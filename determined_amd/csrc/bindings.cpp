@@ -214,6 +214,13 @@ extern "C" void damd_debug_launch(float*, int, int, hipStream_t);
 // launchers (decoder.hip)
 extern "C" void damd_rope_qk_launch(const void*, const void*, void*, void*, const void*, const void*, const int64_t*,
                                     int, int, int, int, int, int, int, hipStream_t);
+extern "C" void damd_rope_norm_fwd_launch(const void*, const void*, void*, void*, const void*, const void*, const void*,
+                                          const void*, const int64_t*, int, int, int, int, int, int, int, float,
+                                          hipStream_t);
+extern "C" int damd_rope_norm_bwd_blocks(int64_t);
+extern "C" int damd_rope_norm_bwd_launch(const void*, const void*, const void*, const void*, void*, void*, const void*,
+                                         const void*, const void*, const void*, float*, const int64_t*, int, int, int,
+                                         int, int, int, int, float, hipStream_t);
 extern "C" void damd_swiglu_fwd_launch(const void*, const void*, void*, int64_t, int, int64_t, int64_t, hipStream_t);
 extern "C" void damd_swiglu_bwd_launch(const void*, const void*, const void*, void*, void*, int64_t, int, int64_t,
                                        int64_t, hipStream_t);
@@ -2004,6 +2011,79 @@ std::vector<at::Tensor> rope_qk(const at::Tensor& q, const at::Tensor& k, const 
   return {oq.permute({0, 2, 1, 3}), ok.permute({0, 2, 1, 3})};
 }
 
+// a per-head norm weight: contiguous [D], bf16 or fp32, 16-byte aligned, on q's device
+bool rope_norm_weight_ok(const at::Tensor& w, const at::Tensor& q) {
+  return w.is_cuda() && w.device() == q.device() && w.dim() == 1 && w.size(0) == q.size(3) && w.is_contiguous() &&
+         (w.scalar_type() == at::kFloat || w.scalar_type() == at::kBFloat16) && aligned16(w);
+}
+
+// rope_supported plus the two norm weights ([D], one dtype) and at least one token
+bool rope_norm_supported(const at::Tensor& q, const at::Tensor& k, const at::Tensor& cos, const at::Tensor& sin,
+                         const at::Tensor& wq, const at::Tensor& wk) {
+  return rope_supported(q, k, cos, sin) && q.numel() > 0 && rope_norm_weight_ok(wq, q) && rope_norm_weight_ok(wk, q) &&
+         wq.scalar_type() == wk.scalar_type();
+}
+
+void check_rope_norm(const at::Tensor& q, const at::Tensor& k, const at::Tensor& cos, const at::Tensor& sin,
+                     const at::Tensor& wq, const at::Tensor& wk, const char* who) {
+  TORCH_CHECK(attn_supported(q) && attn_supported(k), who, ": q / k need bf16 [B,H,T,D] GPU tensors, D in {64,128}, "
+              "contiguous D, 16-byte aligned strides");
+  TORCH_CHECK(rope_supported(q, k, cos, sin) && q.numel() > 0, who, ": k must be [B, Hkv, T, D] with q's B, T, D and "
+              "Hkv dividing q's ", q.size(1), " heads, cos / sin fp32 or bf16 [Bc, T, D] GPU tensors of one dtype with "
+              "Bc in {1, B}, contiguous D and 16-byte aligned rows, at least one token");
+  TORCH_CHECK(rope_norm_weight_ok(wq, q) && rope_norm_weight_ok(wk, q) && wq.scalar_type() == wk.scalar_type(),
+              who, ": the norm weights must be contiguous [", q.size(3), "] GPU tensors, both bf16 or both fp32");
+}
+
+// (q_rot, k_rot) = rotary(rms_norm(q, wq), rms_norm(k, wk)), the norm over D per head row (Qwen3's
+// q_norm / k_norm).  Outputs are [B,H,T,D] views of fresh [B,T,H,D] memory.
+std::vector<at::Tensor> rope_norm_qk(const at::Tensor& q, const at::Tensor& k, const at::Tensor& cos,
+                                     const at::Tensor& sin, const at::Tensor& wq, const at::Tensor& wk, double eps) {
+  check_rope_norm(q, k, cos, sin, wq, wk, "rope_norm_qk");
+  const int64_t B = q.size(0), H = q.size(1), T = q.size(2), D = q.size(3), Hkv = k.size(1);
+  auto oq = at::empty({B, T, H, D}, q.options());
+  auto ok = at::empty({B, T, Hkv, D}, q.options());
+  const int64_t strides[10] = {q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
+                               cos.size(0) == 1 ? 0 : cos.stride(0), cos.stride(1),
+                               sin.size(0) == 1 ? 0 : sin.stride(0), sin.stride(1)};
+  damd_rope_norm_fwd_launch(q.data_ptr(), k.data_ptr(), oq.data_ptr(), ok.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+                            wq.data_ptr(), wk.data_ptr(), strides, static_cast<int>(B), static_cast<int>(T),
+                            static_cast<int>(H), static_cast<int>(Hkv), static_cast<int>(D),
+                            cos.scalar_type() == at::kBFloat16 ? 1 : 0, dtype_code(wq), static_cast<float>(eps),
+                            cur_stream());
+  return {oq.permute({0, 2, 1, 3}), ok.permute({0, 2, 1, 3})};
+}
+
+// (dq, dk, dwq, dwk) of rope_norm_qk for the upstream gradients gq, gk (views like q, k); rstd is
+// recomputed from q, k.  dq / dk are [B,H,T,D] views of [B,T,H,D] memory; dwq / dwk are the two rows
+// of one [2, D] tensor in the weights' dtype, summed in a fixed order (no atomics).
+std::vector<at::Tensor> rope_norm_qk_bwd(const at::Tensor& gq, const at::Tensor& gk, const at::Tensor& q,
+                                         const at::Tensor& k, const at::Tensor& cos, const at::Tensor& sin,
+                                         const at::Tensor& wq, const at::Tensor& wk, double eps) {
+  check_rope_norm(q, k, cos, sin, wq, wk, "rope_norm_qk_bwd");
+  TORCH_CHECK(attn_supported(gq) && attn_supported(gk) && gq.sizes() == q.sizes() && gk.sizes() == k.sizes() &&
+                  gq.device() == q.device() && gk.device() == q.device(),
+              "rope_norm_qk_bwd: gq / gk need q's / k's shape and device, bf16, contiguous D, 16-byte aligned strides");
+  const int64_t B = q.size(0), H = q.size(1), T = q.size(2), D = q.size(3), Hkv = k.size(1);
+  auto dq = at::empty({B, T, H, D}, q.options());
+  auto dk = at::empty({B, T, Hkv, D}, q.options());
+  auto dw = at::empty({2, D}, wq.options());
+  auto part = at::empty({damd_rope_norm_bwd_blocks(B * T), 2 * D}, q.options().dtype(at::kFloat));
+  const int64_t strides[16] = {q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2),
+                               cos.size(0) == 1 ? 0 : cos.stride(0), cos.stride(1),
+                               sin.size(0) == 1 ? 0 : sin.stride(0), sin.stride(1),
+                               gq.stride(0), gq.stride(1), gq.stride(2), gk.stride(0), gk.stride(1), gk.stride(2)};
+  const int W = damd_rope_norm_bwd_launch(gq.data_ptr(), gk.data_ptr(), q.data_ptr(), k.data_ptr(), dq.data_ptr(),
+                                          dk.data_ptr(), cos.data_ptr(), sin.data_ptr(), wq.data_ptr(), wk.data_ptr(),
+                                          part.data_ptr<float>(), strides, static_cast<int>(B), static_cast<int>(T),
+                                          static_cast<int>(H), static_cast<int>(Hkv), static_cast<int>(D),
+                                          cos.scalar_type() == at::kBFloat16 ? 1 : 0, dtype_code(wq),
+                                          static_cast<float>(eps), cur_stream());
+  damd_norm_wgrad_finalize_launch(part.data_ptr<float>(), nullptr, W, static_cast<int>(2 * D), dw.data_ptr(), nullptr,
+                                  dtype_code(wq), cur_stream());
+  return {dq.permute({0, 2, 1, 3}), dk.permute({0, 2, 1, 3}), dw[0], dw[1]};
+}
+
 // gate, up: bf16 [M, I] GPU tensors, contiguous columns, I % 8 == 0, 16-byte aligned rows (the two
 // halves of a packed [M, 2I] projection qualify)
 bool swiglu_half_ok(const at::Tensor& t) {
@@ -2067,6 +2147,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gelu_bwd_bias", &gelu_bwd_bias, py::arg("dg"), py::arg("h"), py::arg("bias_dtype"), py::arg("exact") = false);
   m.def("rope_supported", &rope_supported);
   m.def("rope_qk", &rope_qk, py::arg("q"), py::arg("k"), py::arg("cos"), py::arg("sin"), py::arg("backward") = false);
+  m.def("rope_norm_supported", &rope_norm_supported);
+  m.def("rope_norm_qk", &rope_norm_qk, py::arg("q"), py::arg("k"), py::arg("cos"), py::arg("sin"), py::arg("wq"),
+        py::arg("wk"), py::arg("eps"));
+  m.def("rope_norm_qk_bwd", &rope_norm_qk_bwd, py::arg("gq"), py::arg("gk"), py::arg("q"), py::arg("k"),
+        py::arg("cos"), py::arg("sin"), py::arg("wq"), py::arg("wk"), py::arg("eps"));
   m.def("swiglu_supported", &swiglu_supported);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);

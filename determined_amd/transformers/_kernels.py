@@ -10,12 +10,18 @@
   pass their un-repeated ``[B, Hkv, T, D]`` key / value straight to the grouped-query kernels, and
   sliding-window layers (``sliding_window=`` from Mistral / Qwen2-style attention) run the kernels'
   band mode (``window=``);
-* ``LlamaRMSNorm`` / ``MistralRMSNorm`` / ``Qwen2RMSNorm`` -> ``FusedRMSNorm`` (``csrc/norm.hip``);
+* ``LlamaRMSNorm`` / ``MistralRMSNorm`` / ``Qwen2RMSNorm`` / ``Qwen3RMSNorm`` / ``Qwen3MoeRMSNorm`` ->
+  ``FusedRMSNorm`` (``csrc/norm.hip``);
 * ``LlamaAttention`` / ``MistralAttention`` / ``Qwen2Attention`` -> a forward whose rotary embedding of
   the query and key is ONE ``csrc/decoder.hip`` kernel (``ops.rotary.apply_rotary``: strided
   projection views in, the attention kernels' ``[B, T, H, D]`` memory out; the backward is one launch
   for dQ and dK); a KV cache (the one HF creates by default, ``use_cache=True``, included) is updated
-  with the rotated key as in the stock forward; extra sub-modules (q / k norms) take the original forward;
+  with the rotated key as in the stock forward; other extra sub-modules take the original forward;
+* ``Qwen3Attention`` / ``Qwen3MoeAttention`` (the same forward in transformers 5.15) -> that forward
+  with the ``q_norm`` / ``k_norm`` RMSNorm over the head dim fused into the rotary kernel: the Q / K
+  projection outputs are read once and the attention layout written once, the backward recomputes the
+  row scale and sums the two norm-weight gradients deterministically (no atomics); fp32 / CPU / other
+  head dims run HF's composition;
 * gated MLPs (``gate_proj`` / ``up_proj`` / ``down_proj`` with a SiLU ``act_fn``) ->
   ``down_proj(ops.fused.swiglu(gate, up))``: one ``csrc/decoder.hip`` kernel each way, two saved
   ``[tokens, intermediate]`` activations instead of three (other activations keep their forward);
@@ -167,8 +173,15 @@ def _swiglu_mlp_forward(self, x: torch.Tensor) -> torch.Tensor:
     return self.down_proj(swiglu(self.gate_proj(x), self.up_proj(x)))
 
 
-_ROPE_ATTENTIONS = ("LlamaAttention", "MistralAttention", "Qwen2Attention")
+# ``Qwen3MoeAttention.forward`` is ``Qwen3Attention.forward`` line for line in transformers 5.15
+_QK_NORM_ATTENTIONS = ("Qwen3Attention", "Qwen3MoeAttention")
+_ROPE_ATTENTIONS = ("LlamaAttention", "MistralAttention", "Qwen2Attention") + _QK_NORM_ATTENTIONS
 _ROPE_ATTENTION_CHILDREN = {"q_proj", "k_proj", "v_proj", "o_proj"}
+
+
+def _norm_eps(norm: nn.Module) -> float:
+    """The epsilon of a q / k norm: ``eps`` once swapped for ``FusedRMSNorm``, ``variance_epsilon`` on a stock module."""
+    return norm.eps if hasattr(norm, "eps") else norm.variance_epsilon
 
 
 def _rope_attention_forward(self, hidden_states: torch.Tensor, position_embeddings: Any = None,
@@ -179,15 +192,21 @@ def _rope_attention_forward(self, hidden_states: torch.Tensor, position_embeddin
     go straight to the registered attention interface.  A KV cache is updated with the rotated key and
     the value as in the stock forward (HF's model forward creates one per call unless
     ``use_cache=False``, in training too; its ``update`` copies both, so training steps are better run
-    with ``use_cache=False``).  A module with children this forward does not know (q / k norms, ...)
-    takes the original forward."""
+    with ``use_cache=False``).  ``Qwen3Attention`` / ``Qwen3MoeAttention`` hand the same call the weights
+    and epsilon of their ``q_norm`` / ``k_norm`` (an RMSNorm over the head dim of every query and key
+    head, applied before the rotation): norm and rotation are then ONE kernel, and the norm modules' own
+    forwards are not called.  A module with children this forward does not know takes the original
+    forward."""
     import sys
 
     from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
 
     from determined_amd.ops.rotary import apply_rotary
 
-    if position_embeddings is None or set(self._modules) != _ROPE_ATTENTION_CHILDREN:
+    cls = type(self).__name__
+    normed = cls in _QK_NORM_ATTENTIONS  # q_norm / k_norm over the head dim, fused into the rotary kernel
+    children = _ROPE_ATTENTION_CHILDREN | {"q_norm", "k_norm"} if normed else _ROPE_ATTENTION_CHILDREN
+    if position_embeddings is None or set(self._modules) != children:
         return self._damd_orig_forward(hidden_states, position_embeddings, attention_mask, past_key_values, **kwargs)
     input_shape = hidden_states.shape[:-1]
     hidden_shape = (*input_shape, -1, self.head_dim)
@@ -195,13 +214,15 @@ def _rope_attention_forward(self, hidden_states: torch.Tensor, position_embeddin
     key = self.k_proj(hidden_states).view(hidden_shape).transpose(1, 2)
     value = self.v_proj(hidden_states).view(hidden_shape).transpose(1, 2)
     cos, sin = position_embeddings
-    query, key = apply_rotary(query, key, cos, sin)
+    if normed:
+        query, key = apply_rotary(query, key, cos, sin, self.q_norm.weight, self.k_norm.weight, _norm_eps(self.q_norm))
+    else:
+        query, key = apply_rotary(query, key, cos, sin)
     if past_key_values is not None:
         key, value = past_key_values.update(key, value, self.layer_idx)
-    cls = type(self).__name__
     if cls == "MistralAttention":
         kwargs["sliding_window"] = getattr(self.config, "sliding_window", None)
-    elif cls == "Qwen2Attention":
+    elif cls == "Qwen2Attention" or normed:
         kwargs["sliding_window"] = self.sliding_window
     attention = ALL_ATTENTION_FUNCTIONS.get_interface(self.config._attn_implementation,
                                                       sys.modules[type(self).__module__].eager_attention_forward)
@@ -222,7 +243,7 @@ def _to_fused(ln: nn.LayerNorm) -> FusedLayerNorm:
 
 
 # ``weight * x / rms(x)`` norms, by class name: not ``*RMSNorm`` -- Gemma's scales by ``1 + weight``
-_RMS_NORMS = ("LlamaRMSNorm", "MistralRMSNorm", "Qwen2RMSNorm")
+_RMS_NORMS = ("LlamaRMSNorm", "MistralRMSNorm", "Qwen2RMSNorm", "Qwen3RMSNorm", "Qwen3MoeRMSNorm")
 
 
 def _to_fused_rms(norm: nn.Module) -> FusedRMSNorm:
