@@ -22,6 +22,18 @@ def _ext():
     return ops.ext()
 
 
+def _masked_mean_ce(logits2: torch.Tensor, labels1: torch.Tensor, ignore_index: int) -> torch.Tensor:
+    """The PyTorch path of both losses, with the fused kernels' label rules: a label outside
+    ``[0, V)`` is ignored like ``ignore_index`` (``F.cross_entropy`` alone raises on it, or trips a
+    device-side assert), and the mean is over ``max(n_valid, 1)`` rows (0, not NaN, when none is
+    labelled)."""
+    V = logits2.shape[-1]
+    valid = (labels1 != ignore_index) & (labels1 >= 0) & (labels1 < V)
+    labels1 = torch.where(valid, labels1, torch.full_like(labels1, ignore_index))
+    total = F.cross_entropy(logits2, labels1, ignore_index=ignore_index, reduction="sum")
+    return total / valid.sum().clamp(min=1)
+
+
 class _LMCrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, vocab_size: int, ignore_index: int, inplace_grad: bool):
@@ -44,15 +56,15 @@ class _LMCrossEntropyFn(torch.autograd.Function):
 def lm_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, vocab_size: int, ignore_index: int = -100,
                      inplace_grad: bool = True) -> torch.Tensor:
     """Mean cross-entropy of ``logits[:, t]`` against ``labels[:, t + 1]`` over the first
-    ``vocab_size`` columns (padded columns excluded)."""
-    if logits.is_cuda and logits.dtype == torch.bfloat16 and logits.is_contiguous() and logits.shape[-1] % 8 == 0:
+    ``vocab_size`` columns (padded columns excluded).  A label equal to ``ignore_index`` or outside
+    ``[0, vocab_size)`` is ignored; the mean is over the remaining targets (0 when there is none)."""
+    if logits.is_cuda and logits.dtype == torch.bfloat16 and logits.is_contiguous() and logits.shape[-1] % 8 == 0 \
+            and logits.data_ptr() % 16 == 0:  # the kernels load 16-byte vectors
         return _LMCrossEntropyFn.apply(logits, labels.contiguous(), int(vocab_size), int(ignore_index),
                                        bool(inplace_grad))
-    V = logits.shape[-1]
     lg = logits[:, :-1, :vocab_size].reshape(-1, vocab_size)
     lg = lg.to(torch.promote_types(lg.dtype, torch.float32))
-    del V
-    return F.cross_entropy(lg, labels[:, 1:].reshape(-1), ignore_index=ignore_index)
+    return _masked_mean_ce(lg, labels[:, 1:].reshape(-1), ignore_index)
 
 
 class _TokenCEFn(torch.autograd.Function):
@@ -79,15 +91,18 @@ class _TokenCEFn(torch.autograd.Function):
 
 def token_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = -100,
                         inplace_grad: bool = False) -> torch.Tensor:
-    """``F.cross_entropy(logits.view(-1, V), labels.view(-1), ignore_index=...)`` (mean over the
-    labelled tokens) -- the masked-LM / token-classification loss.  bf16 GPU logits with an even V
-    run the fused kernels (csrc/fused.hip ce_fwd / ce_bwd: only labelled rows are read, no fp32 copy
-    of the logits; ``inplace_grad`` writes the gradient over them); anything else runs PyTorch's."""
+    """The masked-LM / token-classification loss: as ``F.cross_entropy(logits.view(-1, V),
+    labels.view(-1), ignore_index=...)`` (mean over the labelled tokens), except that a label outside
+    ``[0, V)`` is ignored like ``ignore_index`` instead of raising, and the loss is 0, not NaN, when
+    no token is labelled.  bf16 GPU logits with an even V run the fused kernels (csrc/fused.hip
+    ce_fwd / ce_bwd: only labelled rows are read, no fp32 copy of the logits; ``inplace_grad`` writes
+    the gradient over them); anything else runs PyTorch's, with the same label rules."""
     V = logits.shape[-1]
-    if logits.is_cuda and logits.dtype == torch.bfloat16 and V % 2 == 0 and logits.is_contiguous():
+    if logits.is_cuda and logits.dtype == torch.bfloat16 and V % 2 == 0 and logits.is_contiguous() \
+            and logits.data_ptr() % 4 == 0:  # the kernels load bf16 pairs
         return _TokenCEFn.apply(logits.view(-1, V), labels.reshape(-1).contiguous().long(), int(ignore_index),
                                 bool(inplace_grad))
-    return F.cross_entropy(logits.reshape(-1, V).float(), labels.reshape(-1), ignore_index=ignore_index)
+    return _masked_mean_ce(logits.reshape(-1, V).float(), labels.reshape(-1), ignore_index)
 
 
 # Split-K weight gradients: dW = dY^T X reduces over all M tokens into a small N x K output, too few
