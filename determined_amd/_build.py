@@ -31,7 +31,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXX = os.environ.get("CXX", "g++")
 ARCH = os.environ.get("DAMD_OFFLOAD_ARCH", "gfx950")
 
-HIP_SOURCES = ["optim.hip", "norm.hip", "bn.hip", "attention.hip", "attention_decode.hip", "attention_chunk.hip", "fused.hip", "decoder.hip", "conv_stem.hip", "conv_igemm.hip", "conv3x3v2.hip"]
+HIP_SOURCES = ["optim.hip", "norm.hip", "bn.hip", "attention.hip", "attention_decode.hip", "attention_chunk.hip", "attention_d256.hip", "fused.hip", "decoder.hip", "conv_stem.hip", "conv_igemm.hip", "conv3x3v2.hip"]
 # MFMA kernels whose accumulators are also touched by VALU code (online softmax, rescales):
 # keep them in the unified VGPR file instead of AGPRs, which otherwise costs a
 # v_accvgpr_read/write pair per element per tile (attention: 450 copies per kv tile) and
@@ -40,12 +40,13 @@ HIP_SOURCES = ["optim.hip", "norm.hip", "bn.hip", "attention.hip", "attention_de
 # accumulator arithmetic otherwise compiles to them, and some forms have given wrong results on
 # MI355X with no error; the scalar forms are bit-identical.  attention_decode.hip and
 # attention_chunk.hip share its fragment helpers (csrc/attention_frag.h) and accumulator arithmetic, and
-# are built with the same flags.
+# are built with the same flags; so is attention_d256.hip (the head dim 256 kernels).
 _ATTN_FLAGS = ["-mllvm", "-amdgpu-mfma-vgpr-form=1", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_EXTRA_FLAGS = {
     "attention.hip": _ATTN_FLAGS,
     "attention_decode.hip": _ATTN_FLAGS,
     "attention_chunk.hip": _ATTN_FLAGS,
+    "attention_d256.hip": _ATTN_FLAGS,
     "conv_stem.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
 }
 HOST_SOURCES = ["bindings.cpp", "blaslt.cpp"]

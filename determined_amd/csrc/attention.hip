@@ -957,6 +957,16 @@ int damd_attn_gqa_split(int B, int Hkv, int G, int T) {
   return S;
 }
 
+// delta = rowsum(dO . O) for the D = 256 backward (attention_d256.hip); so / sdo: (b, h, t) strides.
+void damd_attn_delta256_launch(const void* o, const int64_t* so, const void* dout, const int64_t* sdo, float* delta,
+                               int B, int H, int T, hipStream_t st) {
+  const int64_t rows = static_cast<int64_t>(B) * H * T;
+  const int blocks = static_cast<int>((rows * 32 + 255) / 256);
+  const Strides os{so[0], so[1], so[2]}, ds{sdo[0], sdo[1], sdo[2]};
+  DAMD_LAUNCH((attn_delta_kernel<256>), dim3(blocks), dim3(256), 0, st, static_cast<const bf16_t*>(o), os,
+              static_cast<const bf16_t*>(dout), ds, delta, H, T, rows);
+}
+
 // strides: 4 tensors (q, k, v, o) x (b, h, t) in elements; km: optional [B][kms] key mask.
 // klo .. qhi: the band arrays (all four or none; with them `causal` only feeds attn_qt), rows of
 // band_stride int32 (0: one shared row), padded to a multiple of 128 entries >= T.

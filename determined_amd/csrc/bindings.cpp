@@ -191,6 +191,13 @@ extern "C" void damd_attn_bwd_launch(const void*, const void*, const void*, cons
                                      hipStream_t, const int32_t*, const int32_t*, const int32_t*, const int32_t*,
                                      int64_t);
 // launchers (attention_decode.hip)
+extern "C" void damd_attn256_fwd_launch(const void*, const void*, const void*, void*, float*, const int64_t*, int, int,
+                                        int, int, float, int, const uint8_t*, int64_t, hipStream_t, const int32_t*,
+                                        const int32_t*, const int32_t*, const int32_t*, int64_t);
+extern "C" void damd_attn256_bwd_launch(const void*, const void*, const void*, const void*, const void*, float*,
+                                        float*, void*, void*, void*, const int64_t*, int, int, int, int, float, int,
+                                        const uint8_t*, int64_t, hipStream_t, const int32_t*, const int32_t*,
+                                        const int32_t*, const int32_t*, int64_t);
 extern "C" int damd_attn_decode_split(int, int, int, int, int);
 extern "C" void damd_attn_decode_launch(const void*, const void*, const void*, void*, float*, float*, float*,
                                         const int64_t*, int, int, int, int, int, int, float, int, int, const uint8_t*,
@@ -1481,19 +1488,24 @@ std::vector<at::Tensor> conv1x1_bwd_fused(const at::Tensor& dzn, const at::Tenso
 
 // ---------------------------------------------------------------- flash attention
 // q, k, v, o, ... are [B, H, T, D] views (any batch/head/token strides, contiguous D,
-// 16-byte aligned rows); D in {64, 128}; bf16.
+// 16-byte aligned rows); bf16; D in {64, 128} (attention.hip) or 256 (attention_d256.hip: same-length
+// attn_fwd / attn_bwd without dropout only -- the KV-cache, rotary and packed-QKV kernels stop at 128
+// and add `D <= 128` to this check).
 bool attn_supported(const at::Tensor& t) {
   if (!t.is_cuda() || t.scalar_type() != at::kBFloat16 || t.dim() != 4) return false;
   const int64_t D = t.size(3);
-  if (D != 64 && D != 128) return false;
+  if (D != 64 && D != 128 && D != 256) return false;
   if (t.stride(3) != 1) return false;
   for (int i = 0; i < 3; ++i)
     if (t.stride(i) % 8 != 0) return false;
   return (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15) == 0;
 }
 
+// the kernels that stop at head dim 128: KV-cache attention (decode, chunked prefill) and rotary
+static bool attn_supported_d128(const at::Tensor& t) { return attn_supported(t) && t.size(3) <= 128; }
+
 void check_attn(const at::Tensor& t, const at::Tensor& ref, const char* what) {
-  TORCH_CHECK(attn_supported(t), what, ": unsupported layout (need bf16 [B,H,T,D], D in {64,128}, contiguous D, "
+  TORCH_CHECK(attn_supported(t), what, ": unsupported layout (need bf16 [B,H,T,D], D in {64,128,256}, contiguous D, "
               "16-byte aligned strides)");
   TORCH_CHECK(t.sizes() == ref.sizes(), what, " shape mismatch");
 }
@@ -1501,7 +1513,7 @@ void check_attn(const at::Tensor& t, const at::Tensor& ref, const char* what) {
 // k (and v, dk, dv through check_attn(., k)) against q: [B, Hkv, T, D] with H % Hkv == 0 --
 // grouped-query attention when Hkv < H.
 void check_attn_kv(const at::Tensor& k, const at::Tensor& q) {
-  TORCH_CHECK(attn_supported(k), "k: unsupported layout (need bf16 [B,Hkv,T,D], D in {64,128}, contiguous D, "
+  TORCH_CHECK(attn_supported(k), "k: unsupported layout (need bf16 [B,Hkv,T,D], D in {64,128,256}, contiguous D, "
               "16-byte aligned strides)");
   TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2) && k.size(3) == q.size(3) && k.size(1) > 0 &&
                   q.size(1) % k.size(1) == 0,
@@ -1575,6 +1587,15 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const
   push_strides(s, k);
   push_strides(s, v);
   push_strides(s, o);
+  if (D == 256) {
+    TORCH_CHECK(drop_p == 0.0, "attn_fwd: the head dim 256 kernels have no dropout (dropout_p = ", drop_p, ")");
+    if (B * H * T > 0)
+      damd_attn256_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), s.data(),
+                              static_cast<int>(B), static_cast<int>(H), static_cast<int>(k.size(1)),
+                              static_cast<int>(T), static_cast<float>(scale), causal ? 1 : 0, km, kms, cur_stream(),
+                              bp.p[0], bp.p[1], bp.p[2], bp.p[3], bp.stride);
+    return {o, lse};
+  }
   if (B * H * T > 0)
     damd_attn_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), s.data(),
                          static_cast<int>(B), static_cast<int>(H), static_cast<int>(k.size(1)), static_cast<int>(T),
@@ -1602,6 +1623,19 @@ void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, 
   int64_t kms = 0;
   const uint8_t* km = check_kmask(kmask, q, &kms);
   const BandPtrs bp = check_band(band, q);
+  if (D == 256) {  // attention_d256.hip: one dK/dV kernel for every group size, no head split
+    TORCH_CHECK(drop_p == 0.0, "attn_bwd: the head dim 256 kernels have no dropout (dropout_p = ", drop_p, ")");
+    std::vector<int64_t> s;
+    const at::Tensor* order[] = {&q, &k, &v, &o, &dout, &dk, &dv, &dq};
+    for (const at::Tensor* t : order) push_strides(s, *t);
+    if (B * H * T > 0)
+      damd_attn256_bwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
+                              lse.data_ptr<float>(), delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
+                              dv.data_ptr(), s.data(), static_cast<int>(B), static_cast<int>(H),
+                              static_cast<int>(Hkv), static_cast<int>(T), static_cast<float>(scale), causal ? 1 : 0,
+                              km, kms, cur_stream(), bp.p[0], bp.p[1], bp.p[2], bp.p[3], bp.stride);
+    return;
+  }
   // grouped-query dK/dV with the group's heads split over `split` workgroups: fp32 partials
   int split = 1;
   at::Tensor part;
@@ -1628,7 +1662,7 @@ void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, 
 // q [B, H, Tq, D] at the END of k / v [B, Hkv, Tk, D] (query row i at position Tk - Tq + i), layouts
 // as attn_supported; the packed rows (H / Hkv) * Tq of one K/V head fit two 16-column MFMA tiles.
 bool attn_decode_supported(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
-  if (!attn_supported(q) || !attn_supported(k) || !attn_supported(v)) return false;
+  if (!attn_supported_d128(q) || !attn_supported_d128(k) || !attn_supported_d128(v)) return false;
   if (k.device() != q.device() || v.device() != q.device() || v.sizes() != k.sizes()) return false;
   const int64_t B = q.size(0), H = q.size(1), Tq = q.size(2), Hkv = k.size(1), Tk = k.size(2);
   if (k.size(0) != B || k.size(3) != q.size(3) || Hkv < 1 || H % Hkv != 0) return false;
@@ -1662,7 +1696,7 @@ int64_t attn_decode_split(const at::Tensor& q, const at::Tensor& k, int64_t wind
 std::vector<at::Tensor> attn_decode_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, bool causal,
                                         double scale, const c10::optional<at::Tensor>& kmask, int64_t window,
                                         int64_t split) {
-  TORCH_CHECK(attn_supported(q) && attn_supported(k) && attn_supported(v),
+  TORCH_CHECK(attn_supported_d128(q) && attn_supported_d128(k) && attn_supported_d128(v),
               "attn_decode_fwd: unsupported layout (need bf16 [B,H,T,D] GPU tensors, D in {64,128}, contiguous D, "
               "16-byte aligned strides)");
   TORCH_CHECK(k.device() == q.device() && v.device() == q.device(), "attn_decode_fwd: tensors on different devices");
@@ -1705,7 +1739,7 @@ std::vector<at::Tensor> attn_decode_fwd(const at::Tensor& q, const at::Tensor& k
 // The same tensors and masks as the decode kernels with more than 32 packed rows (attention_chunk.hip):
 // no cap on (H / Hkv) * Tq beyond 32-bit row indices.
 bool attn_chunk_supported(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
-  if (!attn_supported(q) || !attn_supported(k) || !attn_supported(v)) return false;
+  if (!attn_supported_d128(q) || !attn_supported_d128(k) || !attn_supported_d128(v)) return false;
   if (k.device() != q.device() || v.device() != q.device() || v.sizes() != k.sizes()) return false;
   const int64_t B = q.size(0), H = q.size(1), Tq = q.size(2), Hkv = k.size(1), Tk = k.size(2);
   if (k.size(0) != B || k.size(3) != q.size(3) || Hkv < 1 || H % Hkv != 0) return false;
@@ -1717,7 +1751,7 @@ bool attn_chunk_supported(const at::Tensor& q, const at::Tensor& k, const at::Te
 std::vector<at::Tensor> attn_chunk_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, bool causal,
                                        double scale, const c10::optional<at::Tensor>& kmask, int64_t window,
                                        int64_t split) {
-  TORCH_CHECK(attn_supported(q) && attn_supported(k) && attn_supported(v),
+  TORCH_CHECK(attn_supported_d128(q) && attn_supported_d128(k) && attn_supported_d128(v),
               "attn_chunk_fwd: unsupported layout (need bf16 [B,H,T,D] GPU tensors, D in {64,128}, contiguous D, "
               "16-byte aligned strides)");
   TORCH_CHECK(k.device() == q.device() && v.device() == q.device(), "attn_chunk_fwd: tensors on different devices");
@@ -1976,7 +2010,7 @@ bool rope_table_ok(const at::Tensor& c, const at::Tensor& q) {
 // q [B,H,T,D], k [B,Hkv,T,D]: the attention kernels' layout rule (bf16, D in {64,128}, contiguous D,
 // 16-byte aligned strides), H % Hkv == 0; cos, sin [Bc,T,D] of one dtype
 bool rope_supported(const at::Tensor& q, const at::Tensor& k, const at::Tensor& cos, const at::Tensor& sin) {
-  if (!attn_supported(q) || !attn_supported(k) || k.device() != q.device()) return false;
+  if (!attn_supported_d128(q) || !attn_supported_d128(k) || k.device() != q.device()) return false;
   if (k.size(0) != q.size(0) || k.size(2) != q.size(2) || k.size(3) != q.size(3)) return false;
   if (k.size(1) <= 0 || q.size(1) % k.size(1) != 0) return false;
   if (q.size(0) * q.size(2) > INT32_MAX / 4) return false;  // one workgroup per four tokens
@@ -1988,7 +2022,7 @@ bool rope_supported(const at::Tensor& q, const at::Tensor& k, const at::Tensor& 
 // gradients passed as q, k.  Outputs are [B,H,T,D] views of fresh [B,T,H,D] memory.
 std::vector<at::Tensor> rope_qk(const at::Tensor& q, const at::Tensor& k, const at::Tensor& cos, const at::Tensor& sin,
                                 bool backward) {
-  TORCH_CHECK(attn_supported(q) && attn_supported(k), "rope_qk: q / k need bf16 [B,H,T,D] GPU tensors, D in {64,128}, "
+  TORCH_CHECK(attn_supported_d128(q) && attn_supported_d128(k), "rope_qk: q / k need bf16 [B,H,T,D] GPU tensors, D in {64,128}, "
               "contiguous D, 16-byte aligned strides");
   TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2) && k.size(3) == q.size(3) && k.size(1) > 0 &&
                   q.size(1) % k.size(1) == 0,
@@ -2026,7 +2060,7 @@ bool rope_norm_supported(const at::Tensor& q, const at::Tensor& k, const at::Ten
 
 void check_rope_norm(const at::Tensor& q, const at::Tensor& k, const at::Tensor& cos, const at::Tensor& sin,
                      const at::Tensor& wq, const at::Tensor& wk, const char* who) {
-  TORCH_CHECK(attn_supported(q) && attn_supported(k), who, ": q / k need bf16 [B,H,T,D] GPU tensors, D in {64,128}, "
+  TORCH_CHECK(attn_supported_d128(q) && attn_supported_d128(k), who, ": q / k need bf16 [B,H,T,D] GPU tensors, D in {64,128}, "
               "contiguous D, 16-byte aligned strides");
   TORCH_CHECK(rope_supported(q, k, cos, sin) && q.numel() > 0, who, ": k must be [B, Hkv, T, D] with q's B, T, D and "
               "Hkv dividing q's ", q.size(1), " heads, cos / sin fp32 or bf16 [Bc, T, D] GPU tensors of one dtype with "

@@ -1,6 +1,6 @@
 """Causal / full self-attention for the transformer models.
 
-GPU (bf16, head dim 64 or 128): the hand-written MFMA flash-attention kernels in
+GPU (bf16, head dim 64, 128 or 256): the hand-written MFMA flash-attention kernels in
 ``csrc/attention.hip`` (online softmax, no [T, T] matrix in HBM; backward recomputes P from the
 saved log-sum-exp), with an optional key-padding mask (BERT batches) and in-kernel dropout on the
 attention probabilities (a counter-based keep decision recomputed by the backward -- no mask is
@@ -9,6 +9,12 @@ stored).  Grouped-query / multi-query attention: ``k`` / ``v`` with ``Hkv < H`` 
 summed over each group inside the dK/dV kernel.  ``qkv_attention`` (MHA only) takes the packed ``[B, T, 3, H, D]`` projection output directly and
 writes dQ/dK/dV into ONE gradient buffer of that shape, so the backward needs no concatenation of
 three gradients.
+
+Head dim 256 (Gemma-class decoders, bf16): ``flash_attention`` and ``causal_attention`` run the
+kernels of ``csrc/attention_d256.hip`` -- the same masks (causal, key padding, band), grouped-query K/V
+and layouts, tiled for that size (32-key tiles; dK/dV computed per half of the head dim), without
+in-kernel dropout: a call with ``dropout_p > 0`` is treated like an unserved shape.  ``qkv_attention``,
+``cached_attention`` and the rotary kernels stop at 128.
 
 Band masks (``window=`` / ``segment_ids=``): sliding-window attention (query ``q`` sees the keys
 ``q - window + 1 .. q``) and packed documents (several sequences in one ``[B, T]`` row; attention
@@ -58,11 +64,12 @@ def _ext():
     return ops.ext()
 
 
-def _supported(*ts: torch.Tensor) -> bool:
+def _supported(*ts: torch.Tensor, dropout_p: float = 0.0) -> bool:
+    """Whether the same-length kernels serve these tensors; the head dim 256 kernels have no dropout."""
     if not all(t.is_cuda for t in ts):
         return False
     e = _ext()
-    return all(e.attn_supported(t) for t in ts)
+    return all(e.attn_supported(t) for t in ts) and not (dropout_p > 0 and ts[0].shape[-1] == 256)
 
 
 def key_mask(valid: torch.Tensor) -> torch.Tensor:
@@ -250,7 +257,8 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: b
                     scale: Optional[float] = None, key_padding: Optional[torch.Tensor] = None,
                     dropout_p: float = 0.0, window: Optional[int] = None,
                     segment_ids: Optional[torch.Tensor] = None, band: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Fused attention for ``[B, H, T, D]`` bf16 tensors on the GPU (raises if unsupported).
+    """Fused attention for ``[B, H, T, D]`` bf16 tensors on the GPU, ``D`` in {64, 128, 256} (raises if
+    unsupported; ``D = 256`` with ``dropout_p > 0`` is unsupported).
     ``k`` / ``v`` may have ``Hkv`` heads with ``H % Hkv == 0`` (grouped-query / multi-query
     attention: query head ``h`` reads K/V head ``h // (H // Hkv)``; their gradients have ``Hkv``
     heads).  ``key_padding``: a ``key_mask`` tensor (or a ``[B, T]`` validity mask);
@@ -263,10 +271,11 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: b
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else scale
     if window is not None or segment_ids is not None:
         band = _band(q.shape[2], causal, window, segment_ids, q.device, band)
-    if band is not None and not _supported(q, k, v):
+    if band is not None and not _supported(q, k, v, dropout_p=dropout_p):
         return _sdpa_band(q, k, v, band, key_padding, dropout_p, float(scale))
-    if not _supported(q, k, v):
-        raise ValueError("flash_attention needs bf16 GPU tensors [B,H,T,D] with D in {64,128} and a contiguous D")
+    if not _supported(q, k, v, dropout_p=dropout_p):
+        raise ValueError("flash_attention needs bf16 GPU tensors [B,H,T,D] with D in {64,128,256} (256: no dropout) "
+                         "and a contiguous D")
     if key_padding is not None and (key_padding.dtype != torch.uint8 or key_padding.shape[1] % 64):
         key_padding = key_mask(key_padding)
     return _FlashAttnFn.apply(q, k, v, causal, float(scale), key_padding, float(dropout_p),
@@ -282,7 +291,7 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dropout_
     ``flash_attention``)."""
     if window is not None or segment_ids is not None:
         band = _band(q.shape[2], True, window, segment_ids, q.device, band)
-    if q.is_cuda and _supported(q, k, v):
+    if q.is_cuda and _supported(q, k, v, dropout_p=dropout_p):
         return _FlashAttnFn.apply(q, k, v, True, 1.0 / math.sqrt(q.shape[-1]), None, float(dropout_p),
                                   dropout_seed(dropout_p, q.device), band)
     if band is not None:

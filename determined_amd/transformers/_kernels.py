@@ -41,7 +41,11 @@ the key mask of a left-padded batch included --, the chunked-prefill kernel of
 ``csrc/attention_chunk.hip`` for longer chunks (a new turn against a kept cache), and SDPA with the same
 bottom-right aligned mask when a gradient is needed.
 
-Shapes the kernels do not serve (CPU, fp32, head dim not in {64, 128}) fall back to PyTorch SDPA
+Head dim 256 (Gemma-2 / Gemma-3: grouped-query heads, every other layer a sliding window) takes the
+same route to ``csrc/attention_d256.hip`` when keys and queries have one length and the attention
+dropout is 0; its KV-cache steps and rotary embedding stay with PyTorch.
+
+Shapes the kernels do not serve (CPU, fp32, head dim not in {64, 128, 256}) fall back to PyTorch SDPA
 with the equivalent boolean mask.  Reference: the
 HF Trainer path of ``harness/determined/transformers/_hf_callback.py`` runs the stock modules.
 """
@@ -89,9 +93,9 @@ def _damd_attention(module: nn.Module, query: torch.Tensor, key: torch.Tensor, v
     if same_len and kernel_mask and query.shape[1] % key.shape[1] == 0:
         km = attention_mask
         q, k, v = (t if t.stride(-1) == 1 else t.contiguous() for t in (query, key, value))
-        if _supported(q, k, v):
-            o = flash_attention(q, k, v, causal=causal, scale=scaling, key_padding=km,
-                                dropout_p=dropout if module.training else 0.0, window=window)
+        p = dropout if module.training else 0.0
+        if _supported(q, k, v, dropout_p=p):  # head dim 256 with dropout: SDPA below
+            o = flash_attention(q, k, v, causal=causal, scale=scaling, key_padding=km, dropout_p=p, window=window)
             return o.transpose(1, 2), None
     tq, tk = query.shape[2], key.shape[2]
     # a query chunk at the end of a KV cache (generation): the flash-decoding kernels, or SDPA with the same mask
