@@ -52,6 +52,25 @@
 //   the tile body; choosing the body per tile inside ONE loop took 200 VGPRs, 2 waves); dQ QT = 1
 //   118 / 120 (4), QT = 2 196 / 200 (2); dK/dV 134 / 136 (3), grouped-query dK/dV 142 / 148 (3).
 //
+// Logit soft cap (template argument SOFTCAP of the four kernels, instantiated with DROP = false only;
+//   Gemma-2: y = c * tanh(s * scale / c) in place of s * scale): the raw score becomes t = tanh(.) =
+//   1 - 2 / (1 + 2^(s * k1)) right after the S MFMAs (cap_tanh in attention_frag.h: one v_exp_f32 + one
+//   v_rcp_f32 per score; 2^x = inf gives t = 1, never a NaN) and k2 = c * log2(e) takes the place of the
+//   scale in the exp2 argument.  So the cap precedes every mask select (tanh(-inf) = -1 would un-mask a
+//   key), the maskless tile bodies cap too, the online maximum runs over capped values (NOT the
+//   constant c: exp(y - c) underflows for rows near -c) and the saved LSE is that of the capped logits.
+//   Backward: dS = p * (dP - delta) * (1 - t^2), with t, p and dS computed per score in place; dV, delta
+//   and the final * scale of dQ / dK are unchanged.
+//   Registers (VGPRs, full / causal / band; waves per SIMD as the DROP = false, SOFTCAP = false twin
+//   in brackets; no scratch, no spills, LDS unchanged: 20480-20992 B at D = 64, 36864-37376 B at 128):
+//     forward D = 64  QT = 1: 110 / 110 / 104 (4), twin 112 / 108 / 104;  QT = 2: 160 / 160 / 155 (3), twin 154 / 156 / 156
+//     forward D = 128 QT = 1: 162 / 164 / 160 (3), twin 162 / 164 / 164;  QT = 2: 250 / 252 / 240 (2), twin 250 / 252 / 240
+//     dQ      D = 64  QT = 1: 124 / 126 / 120 (4), twin 122 / 124 / 118;  QT = 2: 194 / 198 / 212 (2), twin 194 / 198 / 196
+//     dQ      D = 128 QT = 1: 188 / 190 / 176 (2), twin 188 / 190 / 176;  QT = 2 (only when forced: DAMD_ATTN_QT):
+//                              256 + 31 / 36 / 44 AGPRs (1), twin 256 + 30 / 33 / 28 AGPRs (1)
+//     dK/dV   D = 64: 136 / 117 / 134 (3 / 4 / 3), twin 138 / 116 / 134;  D = 128: 222 / 202 / 205 (2), twin 224 / 210 / 212
+//     dK/dV grouped-query D = 64: 116 / 118 / 142 (4 / 4 / 3), twin 115 / 116 / 142;  D = 128: 205 / 217 / 220 (2), twin 208 / 224 / 226
+//
 // Strides are in elements for (batch, head, token); the head dimension must be contiguous.
 //
 // Key padding (BERT-style batches): an optional byte mask km[b][key] (row stride kms, rows padded to
@@ -114,6 +133,7 @@ struct FwdArgs {
   float scale_log2;  // softmax scale * log2(e)
   KeyMaskDrop md;
   Band band;
+  float k1, k2;  // SOFTCAP (cap c): 2 * log2(e) * scale / c and c * log2(e); see cap_tanh
 };
 
 struct BwdArgs {
@@ -126,6 +146,7 @@ struct BwdArgs {
   float scale, scale_log2;
   KeyMaskDrop md;
   Band band;
+  float k1, k2;  // SOFTCAP: as in FwdArgs
 };
 
 // Key-tile range of a query-major workgroup (forward, dQ) in band mode, rows [q0, q0 + rows): the
@@ -227,8 +248,9 @@ __device__ __forceinline__ void wg_map(int nblk, int G, int& j, int& bh) {
 // ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
-template <int D, int kQT, int MODE, bool DROP>
+template <int D, int kQT, int MODE, bool DROP, bool SOFTCAP>
 __global__ void __launch_bounds__(kThreads) attn_fwd_kernel(FwdArgs a) {
+  static_assert(!(DROP && SOFTCAP), "the soft cap is instantiated without dropout only");
   constexpr bool CAUSAL = MODE == kCausal, BAND = MODE == kBand;
   constexpr int kFwdRows = fwd_rows(kQT);
   constexpr int KP = kLdsStride(D);
@@ -311,7 +333,17 @@ __global__ void __launch_bounds__(kThreads) attn_fwd_kernel(FwdArgs a) {
 #pragma unroll
     for (int qt = 0; qt < kQT; ++qt) {
       const int myq = qw + qt * 16 + c;
-      // raw scores; the softmax scale (> 0) is folded into the exp2 argument: p = 2^(s*c - m)
+      // raw scores; the softmax scale (> 0) is folded into the exp2 argument: p = 2^(s*c - m).
+      // SOFTCAP (masked and maskless bodies alike): s becomes tanh(s * scale / cap) BEFORE the mask
+      // (tanh(-inf) = -1 would un-mask a key) and cap * log2(e) takes the place of the scale; the
+      // online maximum runs over the capped values.
+      if constexpr (SOFTCAP) {
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) s[qt][nt][r] = cap_tanh(s[qt][nt][r] * a.k1);
+      }
+      const float sl = SOFTCAP ? a.k2 : a.scale_log2;
       if constexpr (MASK) {
         const int kmax = CAUSAL ? min(T - 1, myq) : T - 1;
 #pragma unroll
@@ -337,7 +369,7 @@ __global__ void __launch_bounds__(kThreads) attn_fwd_kernel(FwdArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[qt][nt][r]);
       mx = rows_max(mx);
-      const float m_new = fmaxf(m[qt], mx * a.scale_log2);
+      const float m_new = fmaxf(m[qt], mx * sl);
       const float m_use = m_new == -INFINITY ? 0.f : m_new;
       const float alpha = ex2(m[qt] - m_use);
       float rs = 0.f;
@@ -345,7 +377,7 @@ __global__ void __launch_bounds__(kThreads) attn_fwd_kernel(FwdArgs a) {
       for (int nt = 0; nt < 4; ++nt) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float p = ex2(fmaf(s[qt][nt][r], a.scale_log2, -m_use));
+          const float p = ex2(fmaf(s[qt][nt][r], sl, -m_use));
           rs += p;
           if constexpr (DROP)
             s[qt][nt][r] = drop_keep(md_seed(a.md), a.md.thresh, bh32, myq, k0 + nt * 16 + 4 * g + r) ? p : 0.f;
@@ -438,11 +470,12 @@ __global__ void __launch_bounds__(256) attn_delta_kernel(const bf16_t* __restric
 // dk / dv accumulate.  bh = b*H + (query head): the dropout counter.  Band mode: [qlo, qhi) is the
 // query range of the lane's key, and the block [q0, q0 + 64) is interior when it lies inside the
 // range of every key of the workgroup (kr: see band_query_blocks).
-template <int D, int MODE, bool DROP>
+template <int D, int MODE, bool DROP, bool SOFTCAP>
 __device__ __forceinline__ void bwd_block(const BwdArgs& a, const bf16_t* Qs, const bf16_t* dOs, const float* lse2,
                                           const float* dl, const s8 (&kf)[D / 32], const s8 (&vf)[D / 32],
                                           f4 (&dk)[D / 16], f4 (&dv)[D / 16], uint32_t bh, int q0, int k0, int mykey,
                                           bool kvalid, bool has_km, int qlo, int qhi, const QueryBlocks& kr) {
+  static_assert(!(DROP && SOFTCAP), "the soft cap is instantiated without dropout only");
   constexpr bool CAUSAL = MODE == kCausal, BAND = MODE == kBand;
   constexpr int RP = kLdsStride(D);
   const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
@@ -468,7 +501,9 @@ __device__ __forceinline__ void bwd_block(const BwdArgs& a, const bf16_t* Qs, co
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int ql = qt * 16 + 4 * g + r;
-        float p = ex2(fmaf(sacc[r], a.scale_log2, -lse2[ql]));
+        float x = sacc[r], dcap = 1.f;  // SOFTCAP: x = tanh, dcap = 1 - tanh^2, per score in place
+        if constexpr (SOFTCAP) x = cap_tanh(x * a.k1, dcap);
+        float p = ex2(fmaf(x, SOFTCAP ? a.k2 : a.scale_log2, -lse2[ql]));
         if (need_mask)
           p = (!kvalid || (CAUSAL && mykey > q0 + ql) || (BAND && (q0 + ql < qlo || q0 + ql >= qhi))) ? 0.f : p;
         if constexpr (DROP) {
@@ -477,7 +512,7 @@ __device__ __forceinline__ void bwd_block(const BwdArgs& a, const bf16_t* Qs, co
           dS[hq][r] = p * ((keep ? dpacc[r] * a.md.inv_keep : 0.f) - dl[ql]);
         } else {
           P[hq][r] = p;
-          dS[hq][r] = p * (dpacc[r] - dl[ql]);
+          dS[hq][r] = SOFTCAP ? p * (dpacc[r] - dl[ql]) * dcap : p * (dpacc[r] - dl[ql]);
         }
       }
     }
@@ -492,7 +527,7 @@ __device__ __forceinline__ void bwd_block(const BwdArgs& a, const bf16_t* Qs, co
   }
 }
 
-template <int D, int MODE, bool DROP>
+template <int D, int MODE, bool DROP, bool SOFTCAP>
 __global__ void __launch_bounds__(kThreads) attn_bwd_kernel(BwdArgs a) {
   constexpr bool CAUSAL = MODE == kCausal, BAND = MODE == kBand;
   constexpr int RP = kLdsStride(D);
@@ -559,7 +594,7 @@ __global__ void __launch_bounds__(kThreads) attn_bwd_kernel(BwdArgs a) {
       ost.load(dOp, a.sdo.t, q0 + kBlk, T);
     }
 
-    bwd_block<D, MODE, DROP>(a, Qs, dOs, lse2, dl, kf, vf, dk, dv, static_cast<uint32_t>(bh), q0, k0, mykey, kvalid,
+    bwd_block<D, MODE, DROP, SOFTCAP>(a, Qs, dOs, lse2, dl, kf, vf, dk, dv, static_cast<uint32_t>(bh), q0, k0, mykey, kvalid,
                              KMp != nullptr, qlo, qhi, kr);
   }
   if (mykey < T) {
@@ -590,7 +625,7 @@ __global__ void __launch_bounds__(kThreads) attn_bwd_kernel(BwdArgs a) {
 // Head split (a.S > 1, small grids): workgroup part s of S takes the heads [s*G/S, (s+1)*G/S) of
 // the group (uneven when S does not divide G; S <= G, so no part is empty) and writes fp32
 // partials a.part[dk|dv][s][b*Hkv + hkv][key][D]; attn_gqa_sum_kernel adds them in part order.
-template <int D, int MODE, bool DROP>
+template <int D, int MODE, bool DROP, bool SOFTCAP>
 __global__ void __launch_bounds__(kThreads) attn_bwd_gqa_kernel(BwdArgs a) {
   constexpr bool CAUSAL = MODE == kCausal, BAND = MODE == kBand;
   constexpr int RP = kLdsStride(D);
@@ -665,7 +700,7 @@ __global__ void __launch_bounds__(kThreads) attn_bwd_gqa_kernel(BwdArgs a) {
       qst.load(Qb + nh * a.sq.h, a.sq.t, nqb * kBlk, T);
       ost.load(dOb + nh * a.sdo.h, a.sdo.t, nqb * kBlk, T);
     }
-    bwd_block<D, MODE, DROP>(a, Qs, dOs, lse2, dl, kf, vf, dk, dv, static_cast<uint32_t>(bh), q0, k0, mykey, kvalid,
+    bwd_block<D, MODE, DROP, SOFTCAP>(a, Qs, dOs, lse2, dl, kf, vf, dk, dv, static_cast<uint32_t>(bh), q0, k0, mykey, kvalid,
                              KMp != nullptr, qlo, qhi, kr);
     h = nh;
     qb = nqb;
@@ -730,11 +765,13 @@ struct DqArgs {
   float scale, scale_log2;
   KeyMaskDrop md;
   Band band;
+  float k1, k2;  // SOFTCAP: as in FwdArgs
 };
 
 // dQ for a block of kFwdRows query rows (same wave / lane layout as the forward).
-template <int D, int kQT, int MODE, bool DROP>
+template <int D, int kQT, int MODE, bool DROP, bool SOFTCAP>
 __global__ void __launch_bounds__(kThreads) attn_dq_kernel(DqArgs a) {
+  static_assert(!(DROP && SOFTCAP), "the soft cap is instantiated without dropout only");
   constexpr bool CAUSAL = MODE == kCausal, BAND = MODE == kBand;
   constexpr int kFwdRows = fwd_rows(kQT);
   constexpr int KP = kLdsStride(D);
@@ -830,13 +867,15 @@ __global__ void __launch_bounds__(kThreads) attn_dq_kernel(DqArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = k0 + nt * 16 + 4 * g + r;
-          float p = ex2(fmaf(s[qt][nt][r], a.scale_log2, -lse2[qt]));
+          float x = s[qt][nt][r], dcap = 1.f;  // SOFTCAP: x = tanh, dcap = 1 - tanh^2
+          if constexpr (SOFTCAP) x = cap_tanh(x * a.k1, dcap);
+          float p = ex2(fmaf(x, SOFTCAP ? a.k2 : a.scale_log2, -lse2[qt]));
           if (need_mask) p = (BAND ? (key < klo[qt] || key >= khi[qt]) : key > kmax) ? 0.f : p;
           p = ((mw >> (8 * r)) & 0xffu) ? p : 0.f;
           float dpv = dp[qt][nt][r];
           if constexpr (DROP)
             dpv = drop_keep(md_seed(a.md), a.md.thresh, static_cast<uint32_t>(bh), myq, key) ? dpv * a.md.inv_keep : 0.f;
-          s[qt][nt][r] = p * (dpv - dl[qt]);  // dS^T
+          s[qt][nt][r] = SOFTCAP ? p * (dpv - dl[qt]) * dcap : p * (dpv - dl[qt]);  // dS^T
         }
       }
     }
@@ -878,18 +917,20 @@ using namespace damd::attn;
 
 extern "C" {
 
+// DROP and SOFTCAP never together: the binding refuses softcap > 0 with dropout
+// (the head dim / query tiles come last: `64 DAMD_COMMA 1` would split into two arguments here)
+#define DAMD_ATTN_DISPATCH_M(KERNEL, MODE_, GRID, ARGS, ...)                                         \
+  do {                                                                                               \
+    if ((ARGS).md.thresh != 0) DAMD_LAUNCH((KERNEL<__VA_ARGS__, MODE_, true, false>), GRID, dim3(kThreads), 0, st, ARGS); \
+    else if ((ARGS).k2 > 0.f) DAMD_LAUNCH((KERNEL<__VA_ARGS__, MODE_, false, true>), GRID, dim3(kThreads), 0, st, ARGS);  \
+    else DAMD_LAUNCH((KERNEL<__VA_ARGS__, MODE_, false, false>), GRID, dim3(kThreads), 0, st, ARGS);          \
+  } while (0)
+
 #define DAMD_ATTN_DISPATCH_D(KERNEL, D_, GRID, ARGS)                                                \
   do {                                                                                               \
-    if ((ARGS).band.klo != nullptr) {                                                                \
-      if ((ARGS).md.thresh != 0) DAMD_LAUNCH((KERNEL<D_, kBand, true>), GRID, dim3(kThreads), 0, st, ARGS); \
-      else DAMD_LAUNCH((KERNEL<D_, kBand, false>), GRID, dim3(kThreads), 0, st, ARGS);               \
-    } else if (causal) {                                                                             \
-      if ((ARGS).md.thresh != 0) DAMD_LAUNCH((KERNEL<D_, kCausal, true>), GRID, dim3(kThreads), 0, st, ARGS); \
-      else DAMD_LAUNCH((KERNEL<D_, kCausal, false>), GRID, dim3(kThreads), 0, st, ARGS);             \
-    } else {                                                                                         \
-      if ((ARGS).md.thresh != 0) DAMD_LAUNCH((KERNEL<D_, kFull, true>), GRID, dim3(kThreads), 0, st, ARGS); \
-      else DAMD_LAUNCH((KERNEL<D_, kFull, false>), GRID, dim3(kThreads), 0, st, ARGS);               \
-    }                                                                                                \
+    if ((ARGS).band.klo != nullptr) DAMD_ATTN_DISPATCH_M(KERNEL, kBand, GRID, ARGS, D_);             \
+    else if (causal) DAMD_ATTN_DISPATCH_M(KERNEL, kCausal, GRID, ARGS, D_);                          \
+    else DAMD_ATTN_DISPATCH_M(KERNEL, kFull, GRID, ARGS, D_);                                        \
   } while (0)
 
 #define DAMD_ATTN_DISPATCH(KERNEL, GRID, ARGS)                                                       \
@@ -968,6 +1009,8 @@ void damd_attn_delta256_launch(const void* o, const int64_t* so, const void* dou
 }
 
 // strides: 4 tensors (q, k, v, o) x (b, h, t) in elements; km: optional [B][kms] key mask.
+// softcap: the logit cap c (0: none; >= 0, finite and without dropout: checked by the binding), scores
+// become c * tanh(q.k * scale / c) before the masks.
 // klo .. qhi: the band arrays (all four or none; with them `causal` only feeds attn_qt), rows of
 // band_stride int32 (0: one shared row), padded to a multiple of 128 entries >= T.
 // k, v have Hkv heads, H % Hkv == 0 (checked by the binding).
@@ -975,8 +1018,9 @@ void damd_attn_fwd_launch(const void* q, const void* k, const void* v, void* o, 
                           int B, int H, int Hkv, int T, int D, float scale, int causal, const uint8_t* km,
                           int64_t kms, uint32_t seed, const int64_t* seedp, float drop_p, hipStream_t st,
                           const int32_t* klo, const int32_t* khi, const int32_t* qlo, const int32_t* qhi,
-                          int64_t band_stride) {
+                          int64_t band_stride, float softcap) {
   FwdArgs a;
+  a.k1 = cap_k1(scale, softcap); a.k2 = softcap * kLog2e;
   a.q = static_cast<const bf16_t*>(q); a.k = static_cast<const bf16_t*>(k); a.v = static_cast<const bf16_t*>(v);
   a.o = static_cast<bf16_t*>(o); a.lse = lse;
   a.sq = {strides[0], strides[1], strides[2]}; a.sk = {strides[3], strides[4], strides[5]};
@@ -997,7 +1041,7 @@ void damd_attn_bwd_launch(const void* q, const void* k, const void* v, const voi
                           const int64_t* s, int B, int H, int Hkv, int T, int D, float scale, int causal,
                           const uint8_t* km, int64_t kms, uint32_t seed, const int64_t* seedp, float drop_p,
                           hipStream_t st, const int32_t* klo, const int32_t* khi, const int32_t* qlo,
-                          const int32_t* qhi, int64_t band_stride) {
+                          const int32_t* qhi, int64_t band_stride, float softcap) {
   const Strides sq{s[0], s[1], s[2]}, sk{s[3], s[4], s[5]}, sv{s[6], s[7], s[8]}, so{s[9], s[10], s[11]},
       sdo{s[12], s[13], s[14]}, sdk{s[15], s[16], s[17]}, sdv{s[18], s[19], s[20]}, sdq{s[21], s[22], s[23]};
   const int64_t rows = static_cast<int64_t>(B) * H * T;
@@ -1021,6 +1065,7 @@ void damd_attn_bwd_launch(const void* q, const void* k, const void* v, const voi
   a.G = H / Hkv; a.S = a.G > 1 ? split : 1; a.part = part;
   a.md = make_md(km, kms, seed, seedp, drop_p);
   a.band = {klo, khi, qlo, qhi, band_stride};
+  a.k1 = cap_k1(scale, softcap); a.k2 = softcap * kLog2e;
   const int nblk = (T + kBlk - 1) / kBlk;
   if (a.G == 1) {
     dim3 grid(nblk * H * B);
@@ -1042,6 +1087,7 @@ void damd_attn_bwd_launch(const void* q, const void* k, const void* v, const voi
   d.H = H; d.T = T; d.G = a.G; d.scale = scale; d.scale_log2 = scale * kLog2e;
   d.md = a.md;
   d.band = a.band;
+  d.k1 = a.k1; d.k2 = a.k2;
   const int qt = attn_qt(true, B, H, T, D, causal), qrows = fwd_rows(qt);
   dim3 qgrid(((T + qrows - 1) / qrows) * H * B);
   DAMD_ATTN_DISPATCH_QT(attn_dq_kernel, qt, qgrid, d);

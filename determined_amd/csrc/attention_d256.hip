@@ -36,6 +36,18 @@
 //   dK/dV    full / causal / band: 230 / 240 / 242 VGPRs, 35072 B
 // A 64-key tile (64-query block) adds 32 staging VGPRs to each: dQ and dK/dV would pass 256 and
 // drop to one wave per SIMD, which is why the tiles are 32.
+//
+// Logit soft cap (template argument SOFTCAP, Gemma-2: y = c * tanh(s * scale / c) in place of s * scale):
+// the raw score becomes t = tanh(.) = 1 - 2 / (1 + 2^(s * k1)) right after the S MFMAs (cap_tanh in
+// attention_frag.h: one v_exp_f32 + one v_rcp_f32 per score) and c * log2(e) takes the place of the
+// scale in the exp2 argument, so the cap precedes every mask select, the online maximum runs over
+// capped values and the saved LSE is that of the capped logits.  The backward computes t, p and
+// dS = p * (dP - delta) * (1 - t^2) per score in place (no array of t lives across the MFMAs); the
+// final * scale of dQ / dK is unchanged.  SOFTCAP = true, same conditions (no scratch, no spills, no
+// AGPRs, 2 waves per SIMD, same LDS):
+//   forward  full / causal / band: 208 / 214 / 192 VGPRs
+//   dQ       full / causal / band: 238 / 240 / 224 VGPRs
+//   dK/dV    full / causal / band: 234 / 246 / 238 VGPRs
 
 #include "common.h"
 #include "attention_frag.h"
@@ -68,6 +80,7 @@ struct Args {
   Strides sq, sk, sv, so, sdo, sdq, sdk, sdv;
   int H, T, G;  // G = H / Hkv query heads per K/V head
   float scale, scale_log2;
+  float k1, k2;  // SOFTCAP (cap c): 2 * log2(e) * scale / c and c * log2(e); see cap_tanh
   const uint8_t* km;  // [B][kms] key validity, rows padded to a multiple of 64 (nullptr: every key < T is valid)
   int64_t kms;
   Band band;
@@ -154,7 +167,7 @@ __device__ __forceinline__ void store_rows(bf16_t* p, const f4 (&acc)[N], float 
 // ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
-template <int MODE>
+template <int MODE, bool SOFTCAP>
 __global__ void __launch_bounds__(kThreads) fwd_kernel(Args a) {
   constexpr bool CAUSAL = MODE == kCausal, BAND = MODE == kBand;
   __shared__ __attribute__((aligned(16))) bf16_t Ks[kKT * kP];
@@ -206,7 +219,16 @@ __global__ void __launch_bounds__(kThreads) fwd_kernel(Args a) {
 #pragma unroll
       for (int ds = 0; ds < kD / 32; ++ds)
         s[nt] = mfma(*reinterpret_cast<const s8*>(Ks + (nt * 16 + c) * kP + ds * 32 + 8 * g), qf[ds], s[nt]);
-    // raw scores; the softmax scale (> 0) is folded into the exp2 argument: p = 2^(s*c - m)
+    // raw scores; the softmax scale (> 0) is folded into the exp2 argument: p = 2^(s*c - m).
+    // SOFTCAP: s becomes tanh(s * scale / cap) BEFORE the mask (tanh(-inf) = -1 would un-mask a key)
+    // and cap * log2(e) takes the place of the scale; the online maximum runs over the capped values.
+    if constexpr (SOFTCAP) {
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) s[nt][r] = cap_tanh(s[nt][r] * a.k1);
+    }
+    const float sl = SOFTCAP ? a.k2 : a.scale_log2;
     const bool need_mask = k0 + kKT > T || (CAUSAL && k0 + kKT - 1 > qw) ||
                            (BAND && (k0 < bt.in_lo || k0 + kKT > bt.in_hi)) || KMp != nullptr;
     if (need_mask) {
@@ -228,7 +250,7 @@ __global__ void __launch_bounds__(kThreads) fwd_kernel(Args a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[nt][r]);
     mx = rows_max(mx);
-    const float m_new = fmaxf(m, mx * a.scale_log2);
+    const float m_new = fmaxf(m, mx * sl);
     const float m_use = m_new == -INFINITY ? 0.f : m_new;
     const float alpha = ex2(m - m_use);
     float rs = 0.f;
@@ -236,7 +258,7 @@ __global__ void __launch_bounds__(kThreads) fwd_kernel(Args a) {
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        s[nt][r] = ex2(fmaf(s[nt][r], a.scale_log2, -m_use));
+        s[nt][r] = ex2(fmaf(s[nt][r], sl, -m_use));
         rs += s[nt][r];
       }
     l = l * alpha + rs;
@@ -258,7 +280,7 @@ __global__ void __launch_bounds__(kThreads) fwd_kernel(Args a) {
 // dQ: query-major like the forward; S^T = K.Q^T, dP^T = V.dO^T, dS^T = P^T.(dP^T - delta),
 // dQ^T += K^T.dS^T, written once as bf16
 // ------------------------------------------------------------------------------------------
-template <int MODE>
+template <int MODE, bool SOFTCAP>
 __global__ void __launch_bounds__(kThreads) dq_kernel(Args a) {
   constexpr bool CAUSAL = MODE == kCausal, BAND = MODE == kBand;
   __shared__ __attribute__((aligned(16))) bf16_t Ks[kKT * kP];
@@ -325,10 +347,12 @@ __global__ void __launch_bounds__(kThreads) dq_kernel(Args a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = k0 + nt * 16 + 4 * g + r;
-        float p = ex2(fmaf(s[nt][r], a.scale_log2, -lse2));
+        float x = s[nt][r], dcap = 1.f;  // SOFTCAP: x = tanh, dcap = 1 - tanh^2, per score in place
+        if constexpr (SOFTCAP) x = cap_tanh(x * a.k1, dcap);
+        float p = ex2(fmaf(x, SOFTCAP ? a.k2 : a.scale_log2, -lse2));
         if (need_mask)
           p = ((BAND ? (key < klo || key >= khi) : key > kmax) || !((mw >> (8 * r)) & 0xffu)) ? 0.f : p;
-        s[nt][r] = p * (dp[nt][r] - dl);  // dS^T
+        s[nt][r] = SOFTCAP ? p * (dp[nt][r] - dl) * dcap : p * (dp[nt][r] - dl);  // dS^T
       }
     }
     const s8 sb = pack_pair(s[0], s[1]);
@@ -343,7 +367,7 @@ __global__ void __launch_bounds__(kThreads) dq_kernel(Args a) {
 // dK/dV: 64 keys of one (batch, kv head) x one half of D per workgroup, summed over the group's
 // heads in the accumulators
 // ------------------------------------------------------------------------------------------
-template <int MODE>
+template <int MODE, bool SOFTCAP>
 __global__ void __launch_bounds__(kThreads) dkv_kernel(Args a) {
   constexpr bool CAUSAL = MODE == kCausal, BAND = MODE == kBand;
   __shared__ __attribute__((aligned(16))) bf16_t Qs[kQB * kP];
@@ -419,11 +443,13 @@ __global__ void __launch_bounds__(kThreads) dkv_kernel(Args a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int ql = qt * 16 + 4 * g + r;
-        float p = ex2(fmaf(sacc[r], a.scale_log2, -lse2[ql]));
+        float x = sacc[r], dcap = 1.f;  // SOFTCAP: x = tanh, dcap = 1 - tanh^2
+        if constexpr (SOFTCAP) x = cap_tanh(x * a.k1, dcap);
+        float p = ex2(fmaf(x, SOFTCAP ? a.k2 : a.scale_log2, -lse2[ql]));
         if (need_mask)
           p = (!kvalid || (CAUSAL && mykey > q0 + ql) || (BAND && (q0 + ql < qlo || q0 + ql >= qhi))) ? 0.f : p;
         P[qt][r] = p;
-        dS[qt][r] = p * (dpacc[r] - dl[ql]);
+        dS[qt][r] = SOFTCAP ? p * (dpacc[r] - dl[ql]) * dcap : p * (dpacc[r] - dl[ql]);
       }
     }
     // this half's columns: dV^T += dO^T . P ; dK^T += Q^T . dS  (one permuted step of 32 queries)
@@ -453,11 +479,18 @@ using namespace damd::attn256;
 extern "C" void damd_attn_delta256_launch(const void* o, const int64_t* so, const void* dout, const int64_t* sdo,
                                           float* delta, int B, int H, int T, hipStream_t st);
 
-#define DAMD_ATTN256_DISPATCH(KERNEL, GRID, ARGS)                                                   \
-  do {                                                                                              \
-    if ((ARGS).band.klo != nullptr) DAMD_LAUNCH((KERNEL<kBand>), GRID, dim3(kThreads), 0, st, ARGS); \
-    else if (causal) DAMD_LAUNCH((KERNEL<kCausal>), GRID, dim3(kThreads), 0, st, ARGS);             \
-    else DAMD_LAUNCH((KERNEL<kFull>), GRID, dim3(kThreads), 0, st, ARGS);                           \
+#define DAMD_ATTN256_DISPATCH_CAP(KERNEL, CAP, GRID, ARGS)                                                \
+  do {                                                                                                   \
+    if ((ARGS).band.klo != nullptr) DAMD_LAUNCH((KERNEL<kBand, CAP>), GRID, dim3(kThreads), 0, st, ARGS); \
+    else if (causal) DAMD_LAUNCH((KERNEL<kCausal, CAP>), GRID, dim3(kThreads), 0, st, ARGS);             \
+    else DAMD_LAUNCH((KERNEL<kFull, CAP>), GRID, dim3(kThreads), 0, st, ARGS);                           \
+  } while (0)
+
+// softcap > 0 (the binding checked >= 0 and finite) picks the SOFTCAP instantiation
+#define DAMD_ATTN256_DISPATCH(KERNEL, GRID, ARGS)                         \
+  do {                                                                    \
+    if (softcap > 0.f) DAMD_ATTN256_DISPATCH_CAP(KERNEL, true, GRID, ARGS); \
+    else DAMD_ATTN256_DISPATCH_CAP(KERNEL, false, GRID, ARGS);            \
   } while (0)
 
 extern "C" {
@@ -465,11 +498,13 @@ extern "C" {
 // strides: 4 tensors (q, k, v, o) x (b, h, t) in elements; km: optional [B][kms] key mask; klo .. qhi:
 // the band arrays (all four or none), rows of band_stride int32 (0: one shared row) padded to a
 // multiple of 128 entries >= T.  k, v have Hkv heads, H % Hkv == 0 (checked by the binding).
+// softcap: the logit cap c (0: none), scores become c * tanh(q.k * scale / c) before the masks.
 void damd_attn256_fwd_launch(const void* q, const void* k, const void* v, void* o, float* lse, const int64_t* s, int B,
                              int H, int Hkv, int T, float scale, int causal, const uint8_t* km, int64_t kms,
                              hipStream_t st, const int32_t* klo, const int32_t* khi, const int32_t* qlo,
-                             const int32_t* qhi, int64_t band_stride) {
+                             const int32_t* qhi, int64_t band_stride, float softcap) {
   Args a = {};
+  a.k1 = cap_k1(scale, softcap); a.k2 = softcap * kLog2e;
   a.q = static_cast<const bf16_t*>(q); a.k = static_cast<const bf16_t*>(k); a.v = static_cast<const bf16_t*>(v);
   a.o = static_cast<bf16_t*>(o); a.lse = lse;
   a.sq = {s[0], s[1], s[2]}; a.sk = {s[3], s[4], s[5]}; a.sv = {s[6], s[7], s[8]}; a.so = {s[9], s[10], s[11]};
@@ -486,9 +521,10 @@ void damd_attn256_bwd_launch(const void* q, const void* k, const void* v, const 
                              float* lse, float* delta, void* dq, void* dk, void* dv, const int64_t* s, int B, int H,
                              int Hkv, int T, float scale, int causal, const uint8_t* km, int64_t kms, hipStream_t st,
                              const int32_t* klo, const int32_t* khi, const int32_t* qlo, const int32_t* qhi,
-                             int64_t band_stride) {
+                             int64_t band_stride, float softcap) {
   damd_attn_delta256_launch(o, s + 9, dout, s + 12, delta, B, H, T, st);
   Args a = {};
+  a.k1 = cap_k1(scale, softcap); a.k2 = softcap * kLog2e;
   a.q = static_cast<const bf16_t*>(q); a.k = static_cast<const bf16_t*>(k); a.v = static_cast<const bf16_t*>(v);
   a.dout = static_cast<const bf16_t*>(dout); a.lse = lse; a.delta = delta;
   a.dq = static_cast<bf16_t*>(dq); a.dk = static_cast<bf16_t*>(dk); a.dv = static_cast<bf16_t*>(dv);

@@ -46,6 +46,18 @@ __device__ __forceinline__ short bfs(float x) { return cvt2(x, 0.f)[0]; }
 // raw v_exp_f32 (softmax arguments are <= 0 or -inf; no denormal-range fixup needed)
 __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
 
+// Logit soft cap (y = c * tanh(z / c)): t = tanh(z / c) from x = z / c * 2 * log2(e) as 1 - 2 / (1 + 2^x),
+// one v_exp_f32 + one v_rcp_f32; d = 1 - t^2 = 4r(1 - r) with r = 1 / (1 + 2^x), the backward's factor,
+// without the cancellation of 1 - t*t.  2^x overflows to inf for large x: r = 0, t = 1, d = 0 -- no NaN.
+__device__ __forceinline__ float cap_tanh(float x, float& d) {
+  const float r = __builtin_amdgcn_rcpf(1.f + ex2(x));
+  d = 4.f * r * (1.f - r);
+  return fmaf(-2.f, r, 1.f);
+}
+// host side, cap c > 0 (0: none): the kernels' tanh argument is s * k1, their exp2 scale k2 = c * log2(e)
+inline float cap_k1(float scale, float c) { return c > 0.f ? 2.f * kLog2e * scale / c : 0.f; }
+__device__ __forceinline__ float cap_tanh(float x) { return fmaf(-2.f, __builtin_amdgcn_rcpf(1.f + ex2(x)), 1.f); }
+
 // max / sum over the four 16-lane rows of a wave (lanes c, c+16, c+32, c+48): two VALU lane swaps
 // (v_permlane16_swap, v_permlane32_swap) instead of two LDS round trips through ds_bpermute
 __device__ __forceinline__ float rows_max(float x) {

@@ -5,6 +5,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -183,21 +184,21 @@ extern "C" void damd_stem_wgrad_launch(const void*, const void*, float*, void*, 
 extern "C" void damd_attn_fwd_launch(const void*, const void*, const void*, void*, float*, const int64_t*, int, int,
                                      int, int, int, float, int, const uint8_t*, int64_t, uint32_t, const int64_t*,
                                      float, hipStream_t, const int32_t*, const int32_t*, const int32_t*,
-                                     const int32_t*, int64_t);
+                                     const int32_t*, int64_t, float);
 extern "C" int damd_attn_gqa_split(int, int, int, int);
 extern "C" void damd_attn_bwd_launch(const void*, const void*, const void*, const void*, const void*, const float*,
                                      float*, float*, int, void*, void*, void*, const int64_t*, int, int, int, int, int,
                                      float, int, const uint8_t*, int64_t, uint32_t, const int64_t*, float,
                                      hipStream_t, const int32_t*, const int32_t*, const int32_t*, const int32_t*,
-                                     int64_t);
+                                     int64_t, float);
 // launchers (attention_decode.hip)
 extern "C" void damd_attn256_fwd_launch(const void*, const void*, const void*, void*, float*, const int64_t*, int, int,
                                         int, int, float, int, const uint8_t*, int64_t, hipStream_t, const int32_t*,
-                                        const int32_t*, const int32_t*, const int32_t*, int64_t);
+                                        const int32_t*, const int32_t*, const int32_t*, int64_t, float);
 extern "C" void damd_attn256_bwd_launch(const void*, const void*, const void*, const void*, const void*, float*,
                                         float*, void*, void*, void*, const int64_t*, int, int, int, int, float, int,
                                         const uint8_t*, int64_t, hipStream_t, const int32_t*, const int32_t*,
-                                        const int32_t*, const int32_t*, int64_t);
+                                        const int32_t*, const int32_t*, int64_t, float);
 extern "C" int damd_attn_decode_split(int, int, int, int, int);
 extern "C" void damd_attn_decode_launch(const void*, const void*, const void*, void*, float*, float*, float*,
                                         const int64_t*, int, int, int, int, int, int, float, int, int, const uint8_t*,
@@ -1568,13 +1569,23 @@ BandPtrs check_band(const c10::optional<at::Tensor>& band, const at::Tensor& q) 
   return r;
 }
 
+// Logit soft cap c (Gemma-2): scores become c * tanh(q.k * scale / c) before the masks; 0 = off.
+// The capped kernels are instantiated without dropout.
+void check_softcap(double softcap, double drop_p, const char* what) {
+  TORCH_CHECK(std::isfinite(softcap) && softcap >= 0.0, what, ": softcap must be finite and >= 0 (got ", softcap, ")");
+  TORCH_CHECK(!(softcap > 0.0 && drop_p > 0.0), what, ": softcap (", softcap, ") with dropout (drop_p = ", drop_p,
+              ") has no kernel");
+}
+
 std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, bool causal,
                                  double scale, const c10::optional<at::Tensor>& kmask, double drop_p, int64_t seed,
-                                 const c10::optional<at::Tensor>& seed_t, const c10::optional<at::Tensor>& band) {
+                                 const c10::optional<at::Tensor>& seed_t, const c10::optional<at::Tensor>& band,
+                                 double softcap) {
   check_attn(q, q, "q");
   check_attn_kv(k, q);
   check_attn(v, k, "v");
   TORCH_CHECK(drop_p >= 0.0 && drop_p < 1.0, "dropout probability must be in [0, 1)");
+  check_softcap(softcap, drop_p, "attn_fwd");
   int64_t kms = 0;
   const uint8_t* km = check_kmask(kmask, q, &kms);
   const BandPtrs bp = check_band(band, q);
@@ -1593,7 +1604,7 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const
       damd_attn256_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), s.data(),
                               static_cast<int>(B), static_cast<int>(H), static_cast<int>(k.size(1)),
                               static_cast<int>(T), static_cast<float>(scale), causal ? 1 : 0, km, kms, cur_stream(),
-                              bp.p[0], bp.p[1], bp.p[2], bp.p[3], bp.stride);
+                              bp.p[0], bp.p[1], bp.p[2], bp.p[3], bp.stride, static_cast<float>(softcap));
     return {o, lse};
   }
   if (B * H * T > 0)
@@ -1601,14 +1612,15 @@ std::vector<at::Tensor> attn_fwd(const at::Tensor& q, const at::Tensor& k, const
                          static_cast<int>(B), static_cast<int>(H), static_cast<int>(k.size(1)), static_cast<int>(T),
                          static_cast<int>(D), static_cast<float>(scale), causal ? 1 : 0, km, kms,
                          static_cast<uint32_t>(seed), seed_ptr(seed_t, q), static_cast<float>(drop_p), cur_stream(),
-                         bp.p[0], bp.p[1], bp.p[2], bp.p[3], bp.stride);
+                         bp.p[0], bp.p[1], bp.p[2], bp.p[3], bp.stride, static_cast<float>(softcap));
   return {o, lse};
 }
 
 void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
               const at::Tensor& o, const at::Tensor& lse, at::Tensor& dq, at::Tensor& dk, at::Tensor& dv, bool causal,
               double scale, const c10::optional<at::Tensor>& kmask, double drop_p, int64_t seed,
-              const c10::optional<at::Tensor>& seed_t, const c10::optional<at::Tensor>& band) {
+              const c10::optional<at::Tensor>& seed_t, const c10::optional<at::Tensor>& band, double softcap) {
+  check_softcap(softcap, drop_p, "attn_bwd");
   check_attn(q, q, "q");
   check_attn_kv(k, q);
   check_attn(v, k, "v");
@@ -1633,7 +1645,8 @@ void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, 
                               lse.data_ptr<float>(), delta.data_ptr<float>(), dq.data_ptr(), dk.data_ptr(),
                               dv.data_ptr(), s.data(), static_cast<int>(B), static_cast<int>(H),
                               static_cast<int>(Hkv), static_cast<int>(T), static_cast<float>(scale), causal ? 1 : 0,
-                              km, kms, cur_stream(), bp.p[0], bp.p[1], bp.p[2], bp.p[3], bp.stride);
+                              km, kms, cur_stream(), bp.p[0], bp.p[1], bp.p[2], bp.p[3], bp.stride,
+                              static_cast<float>(softcap));
     return;
   }
   // grouped-query dK/dV with the group's heads split over `split` workgroups: fp32 partials
@@ -1655,7 +1668,7 @@ void attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, 
                          dv.data_ptr(), s.data(), static_cast<int>(B), static_cast<int>(H), static_cast<int>(Hkv),
                          static_cast<int>(T), static_cast<int>(D), static_cast<float>(scale), causal ? 1 : 0, km, kms,
                          static_cast<uint32_t>(seed), seed_ptr(seed_t, q), static_cast<float>(drop_p), cur_stream(),
-                         bp.p[0], bp.p[1], bp.p[2], bp.p[3], bp.stride);
+                         bp.p[0], bp.p[1], bp.p[2], bp.p[3], bp.stride, static_cast<float>(softcap));
 }
 
 // ---------------------------------------------------------------- flash-decoding attention (KV cache)
@@ -2192,11 +2205,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_supported", &attn_supported);
   m.def("attn_fwd", &attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("scale"),
         py::arg("kmask") = py::none(), py::arg("drop_p") = 0.0, py::arg("seed") = 0, py::arg("seed_t") = py::none(),
-        py::arg("band") = py::none());
+        py::arg("band") = py::none(), py::arg("softcap") = 0.0);
   m.def("attn_bwd", &attn_bwd, py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("causal"), py::arg("scale"),
         py::arg("kmask") = py::none(), py::arg("drop_p") = 0.0, py::arg("seed") = 0, py::arg("seed_t") = py::none(),
-        py::arg("band") = py::none());
+        py::arg("band") = py::none(), py::arg("softcap") = 0.0);
   m.def("attn_decode_supported", &attn_decode_supported);
   m.def("attn_decode_split", &attn_decode_split, py::arg("q"), py::arg("k"), py::arg("window") = 0);
   m.def("attn_decode_fwd", &attn_decode_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),

@@ -16,6 +16,14 @@ and layouts, tiled for that size (32-key tiles; dK/dV computed per half of the h
 in-kernel dropout: a call with ``dropout_p > 0`` is treated like an unserved shape.  ``qkv_attention``,
 ``cached_attention`` and the rotary kernels stop at 128.
 
+Logit soft cap (``softcap=``, Gemma-2's ``attn_logit_softcapping``): ``softmax(c * tanh(q k^T * scale /
+c) + mask)`` inside the same-length kernels at every head dim, forward and backward -- the cap is
+applied to the MFMA result before the masks (one ``v_exp_f32`` and one ``v_rcp_f32`` per score), the
+online maximum and the saved log-sum-exp are those of the capped logits, and the backward multiplies
+dS by ``1 - tanh^2``.  The capped kernels have no dropout, and the KV-cache kernels no cap: those calls,
+and capped calls on tensors the kernels do not serve, run one fp32 composition
+(``_softcap_attention``), never SDPA, which cannot express the cap.
+
 Band masks (``window=`` / ``segment_ids=``): sliding-window attention (query ``q`` sees the keys
 ``q - window + 1 .. q``) and packed documents (several sequences in one ``[B, T]`` row; attention
 never crosses a document boundary) are both a staircase -- query ``q`` attends one contiguous key
@@ -64,12 +72,44 @@ def _ext():
     return ops.ext()
 
 
-def _supported(*ts: torch.Tensor, dropout_p: float = 0.0) -> bool:
-    """Whether the same-length kernels serve these tensors; the head dim 256 kernels have no dropout."""
+def _supported(*ts: torch.Tensor, dropout_p: float = 0.0, softcap: Optional[float] = None) -> bool:
+    """Whether the same-length kernels serve these tensors; the head dim 256 kernels and the
+    soft-capped ones (``softcap``) have no dropout."""
     if not all(t.is_cuda for t in ts):
         return False
     e = _ext()
-    return all(e.attn_supported(t) for t in ts) and not (dropout_p > 0 and ts[0].shape[-1] == 256)
+    return all(e.attn_supported(t) for t in ts) and not (dropout_p > 0 and (ts[0].shape[-1] == 256 or bool(softcap)))
+
+
+def _softcap_attention(q, k, v, softcap: float, mask, dropout_p: float, scale: float):
+    """The plain composition of soft-capped attention, for every capped call the kernels do not
+    serve (SDPA cannot express the cap): fp32 scores ``softcap * tanh(q k^T * scale / softcap)``,
+    then the mask (bool, True = attend, broadcastable to ``[B, H, Tq, Tk]``; or additive float; or
+    None), softmax, dropout, ``@ v``; K / V repeated for grouped-query heads.  A query with no
+    attendable key gives zeros, as in the kernels."""
+    G = q.shape[1] // k.shape[1]
+    if G > 1:
+        k, v = k.repeat_interleave(G, 1), v.repeat_interleave(G, 1)
+    s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
+    s = softcap * torch.tanh(s / softcap)
+    if mask is not None:
+        s = s.masked_fill(~mask, float("-inf")) if mask.dtype == torch.bool else s + mask
+    p = torch.softmax(s, -1)
+    if mask is not None:
+        p = p.masked_fill(torch.isneginf(s).all(-1, keepdim=True), 0.0)
+    if dropout_p > 0:
+        p = F.dropout(p, dropout_p)
+    return torch.matmul(p, v.float()).to(q.dtype)
+
+
+def _dense_mask(T: int, causal: bool, band, key_padding, device) -> Optional[torch.Tensor]:
+    """The boolean mask (True = attend) of a same-length call: the band (which holds the causal
+    bound) or the causal triangle, and the valid keys; None when every key is attended."""
+    mask = band_mask(band, T) if band is not None else cached_mask(T, T, causal, device=device)
+    if key_padding is not None:
+        kp = key_padding[:, None, None, :T].bool()
+        mask = kp if mask is None else mask & kp
+    return mask
 
 
 def key_mask(valid: torch.Tensor) -> torch.Tensor:
@@ -205,10 +245,11 @@ def dropout_seed(dropout_p: float, device: torch.device):
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, causal: bool, scale: float, km=None, dropout_p: float = 0.0, seed=(0, None),
-                band=None):
-        o, lse = _ext().attn_fwd(q, k, v, causal, scale, km, dropout_p, seed[0], seed[1], band)
+                band=None, softcap: float = 0.0):
+        o, lse = _ext().attn_fwd(q, k, v, causal, scale, km, dropout_p, seed[0], seed[1], band, softcap=softcap)
         ctx.save_for_backward(q, k, v, o, lse)
         ctx.causal, ctx.scale, ctx.km, ctx.dropout_p, ctx.seed, ctx.band = causal, scale, km, dropout_p, seed, band
+        ctx.softcap = softcap
         return o
 
     @staticmethod
@@ -225,8 +266,8 @@ class _FlashAttnFn(torch.autograd.Function):
             dq = torch.empty(B, T, H, D, dtype=q.dtype, device=q.device).permute(0, 2, 1, 3)
             dk, dv = torch.empty(2, B, T, Hkv, D, dtype=q.dtype, device=q.device).permute(0, 1, 3, 2, 4).unbind(0)
         _ext().attn_bwd(do, q, k, v, o, lse, dq, dk, dv, ctx.causal, ctx.scale, ctx.km, ctx.dropout_p, ctx.seed[0],
-                        ctx.seed[1], ctx.band)
-        return dq, dk, dv, None, None, None, None, None, None
+                        ctx.seed[1], ctx.band, softcap=ctx.softcap)
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 class _QKVFlashAttnFn(torch.autograd.Function):
@@ -256,7 +297,8 @@ class _QKVFlashAttnFn(torch.autograd.Function):
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
                     scale: Optional[float] = None, key_padding: Optional[torch.Tensor] = None,
                     dropout_p: float = 0.0, window: Optional[int] = None,
-                    segment_ids: Optional[torch.Tensor] = None, band: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    segment_ids: Optional[torch.Tensor] = None, band: Optional[torch.Tensor] = None,
+                    softcap: Optional[float] = None) -> torch.Tensor:
     """Fused attention for ``[B, H, T, D]`` bf16 tensors on the GPU, ``D`` in {64, 128, 256} (raises if
     unsupported; ``D = 256`` with ``dropout_p > 0`` is unsupported).
     ``k`` / ``v`` may have ``Hkv`` heads with ``H % Hkv == 0`` (grouped-query / multi-query
@@ -267,10 +309,18 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: b
     runs of equal ids), attention stays inside the query's document; ``band``: the prebuilt
     ``band_ranges`` tensor in their place (a model builds it once per forward and hands it to every
     layer).  With any of the three, tensors the kernels do not serve go through SDPA with the same
-    mask instead of raising."""
+    mask instead of raising.  ``softcap`` (Gemma-2's ``attn_logit_softcapping``; None or 0: off): the
+    scores become ``softcap * tanh(q k^T * scale / softcap)`` before the masks, inside the kernels
+    (forward and backward, every mask mode, no dropout); a capped call the kernels do not serve (CPU,
+    fp32, another head dim, ``dropout_p > 0``) runs the fp32 composition ``_softcap_attention`` --
+    never SDPA, which has no cap -- instead of raising."""
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else scale
+    softcap = float(softcap) if softcap else 0.0
     if window is not None or segment_ids is not None:
         band = _band(q.shape[2], causal, window, segment_ids, q.device, band)
+    if softcap and not _supported(q, k, v, dropout_p=dropout_p, softcap=softcap):
+        mask = _dense_mask(q.shape[2], causal, band, key_padding, q.device)
+        return _softcap_attention(q, k, v, softcap, mask, dropout_p, float(scale))
     if band is not None and not _supported(q, k, v, dropout_p=dropout_p):
         return _sdpa_band(q, k, v, band, key_padding, dropout_p, float(scale))
     if not _supported(q, k, v, dropout_p=dropout_p):
@@ -279,21 +329,25 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: b
     if key_padding is not None and (key_padding.dtype != torch.uint8 or key_padding.shape[1] % 64):
         key_padding = key_mask(key_padding)
     return _FlashAttnFn.apply(q, k, v, causal, float(scale), key_padding, float(dropout_p),
-                              dropout_seed(dropout_p, q.device), band)
+                              dropout_seed(dropout_p, q.device), band, softcap)
 
 
 def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dropout_p: float = 0.0,
                      window: Optional[int] = None, segment_ids: Optional[torch.Tensor] = None,
-                     band: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     band: Optional[torch.Tensor] = None, softcap: Optional[float] = None) -> torch.Tensor:
     """``softmax(q k^T / sqrt(d) + causal_mask) v`` for ``[B, H, T, D]`` tensors; ``k`` / ``v`` may be
     ``[B, Hkv, T, D]`` with ``H % Hkv == 0`` (grouped-query attention).  ``window`` / ``segment_ids``:
-    sliding-window / packed-document masks on top of the causal one, or the prebuilt ``band`` (see
-    ``flash_attention``)."""
+    sliding-window / packed-document masks on top of the causal one, or the prebuilt ``band``;
+    ``softcap``: the logit soft cap (see ``flash_attention`` for all four)."""
+    softcap = float(softcap) if softcap else 0.0
     if window is not None or segment_ids is not None:
         band = _band(q.shape[2], True, window, segment_ids, q.device, band)
-    if q.is_cuda and _supported(q, k, v, dropout_p=dropout_p):
+    if q.is_cuda and _supported(q, k, v, dropout_p=dropout_p, softcap=softcap):
         return _FlashAttnFn.apply(q, k, v, True, 1.0 / math.sqrt(q.shape[-1]), None, float(dropout_p),
-                                  dropout_seed(dropout_p, q.device), band)
+                                  dropout_seed(dropout_p, q.device), band, softcap)
+    if softcap:
+        mask = _dense_mask(q.shape[2], True, band, None, q.device)
+        return _softcap_attention(q, k, v, softcap, mask, dropout_p, 1.0 / math.sqrt(q.shape[-1]))
     if band is not None:
         return _sdpa_band(q, k, v, band, None, dropout_p, None)
     if q.is_cuda:
@@ -360,7 +414,7 @@ def _chunk_fwd(q, k, v, causal: bool, scale: float, km, window: int):
 
 def cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
                      scale: Optional[float] = None, key_padding: Optional[torch.Tensor] = None,
-                     window: Optional[int] = None) -> torch.Tensor:
+                     window: Optional[int] = None, softcap: Optional[float] = None) -> torch.Tensor:
     """Attention of a query chunk ``q [B, H, Tq, D]`` at the end of the keys / values ``[B, Hkv, Tk, D]``
     of a KV cache (``Tq <= Tk``, ``H % Hkv == 0``; query row ``i`` at position ``Tk - Tq + i``).  ``causal``:
     keys up to the query's position; ``window`` (needs ``causal``): only its last ``window`` keys;
@@ -370,7 +424,9 @@ def cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: 
     bf16 GPU tensors with ``D`` in {64, 128} run the HIP kernels when no gradient is needed (grad mode
     off, or none of q / k / v requires one): the flash-decoding kernels up to ``(H / Hkv) * Tq = 32``
     packed rows, the chunked-prefill kernel above; a query with no attendable key gives zeros.
-    Everything else goes through SDPA with ``cached_mask``."""
+    Everything else goes through SDPA with ``cached_mask``.  ``softcap`` (None or 0: off): the logit
+    soft cap of ``flash_attention``; the decode and chunk kernels have none, so a capped call runs the
+    fp32 composition ``_softcap_attention`` with ``cached_mask``."""
     if window is not None and not causal:
         raise ValueError("window= needs causal=True")
     if window is not None and window < 1:
@@ -379,6 +435,9 @@ def cached_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: 
     if tq > tk:
         raise ValueError(f"cached_attention: {tq} queries against {tk} keys (the queries are the last keys)")
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else float(scale)
+    if softcap:
+        mask = cached_mask(tq, tk, causal, window, key_padding, q.device)
+        return _softcap_attention(q, k, v, float(softcap), mask, 0.0, scale)
     needs_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v))
     if q.is_cuda and not needs_grad and _ext().attn_chunk_supported(q, k, v):
         km = key_padding

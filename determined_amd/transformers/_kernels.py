@@ -45,6 +45,13 @@ Head dim 256 (Gemma-2 / Gemma-3: grouped-query heads, every other layer a slidin
 same route to ``csrc/attention_d256.hip`` when keys and queries have one length and the attention
 dropout is 0; its KV-cache steps and rotary embedding stay with PyTorch.
 
+Gemma-2's attention logit soft cap (``softcap=self.attn_logit_softcapping`` from ``Gemma2Attention``,
+50 in the released models; head dim 256 for 2B / 9B, 128 for 27B) is an explicit argument of the
+``"damd"`` attention and goes into the same-length kernels (``flash_attention(..., softcap=)``: the cap
+before the masks, forward and backward).  The KV-cache steps, attention dropout with a cap and the
+last fallback run the fp32 composition ``ops.attention._softcap_attention`` with the same mask --
+never SDPA, which cannot express the cap.
+
 Shapes the kernels do not serve (CPU, fp32, head dim not in {64, 128, 256}) fall back to PyTorch SDPA
 with the equivalent boolean mask.  Reference: the
 HF Trainer path of ``harness/determined/transformers/_hf_callback.py`` runs the stock modules.
@@ -57,7 +64,8 @@ from typing import Any, Optional
 import torch
 from torch import nn
 
-from determined_amd.ops.attention import _supported, cached_attention, cached_mask, flash_attention, key_mask
+from determined_amd.ops.attention import (_softcap_attention, _supported, cached_attention, cached_mask,
+                                          flash_attention, key_mask)
 from determined_amd.ops.norm import FusedLayerNorm, FusedRMSNorm, residual_dropout_layer_norm
 
 NAME = "damd"
@@ -83,7 +91,9 @@ def _damd_mask(batch_size: int, q_length: int, kv_length: int, q_offset: int = 0
 
 def _damd_attention(module: nn.Module, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor,
                     attention_mask: Optional[torch.Tensor], dropout: float = 0.0, scaling: Optional[float] = None,
-                    is_causal: Optional[bool] = None, sliding_window: Optional[int] = None, **kwargs: Any):
+                    is_causal: Optional[bool] = None, sliding_window: Optional[int] = None,
+                    softcap: Optional[float] = None, **kwargs: Any):
+    # softcap: Gemma-2's attn_logit_softcapping, scores -> softcap * tanh(scores / softcap) before the masks
     causal = bool(getattr(module, "is_causal", False) if is_causal is None else is_causal)
     same_len = query.shape[2] == key.shape[2]
     # sliding-window layers (Mistral, Qwen2, ...): a query sees the last `sliding_window` keys, itself included
@@ -94,16 +104,19 @@ def _damd_attention(module: nn.Module, query: torch.Tensor, key: torch.Tensor, v
         km = attention_mask
         q, k, v = (t if t.stride(-1) == 1 else t.contiguous() for t in (query, key, value))
         p = dropout if module.training else 0.0
-        if _supported(q, k, v, dropout_p=p):  # head dim 256 with dropout: SDPA below
-            o = flash_attention(q, k, v, causal=causal, scale=scaling, key_padding=km, dropout_p=p, window=window)
+        if _supported(q, k, v, dropout_p=p, softcap=softcap):  # head dim 256 or a cap with dropout: the fallback below
+            o = flash_attention(q, k, v, causal=causal, scale=scaling, key_padding=km, dropout_p=p, window=window,
+                                softcap=softcap)
             return o.transpose(1, 2), None
     tq, tk = query.shape[2], key.shape[2]
     # a query chunk at the end of a KV cache (generation): the flash-decoding kernels, or SDPA with the same mask
     if tq < tk and kernel_mask and query.shape[1] % key.shape[1] == 0 and not (module.training and dropout > 0):
         q, k, v = (t if t.stride(-1) == 1 else t.contiguous() for t in (query, key, value))
-        o = cached_attention(q, k, v, causal=causal, scale=scaling, key_padding=attention_mask, window=window)
+        o = cached_attention(q, k, v, causal=causal, scale=scaling, key_padding=attention_mask, window=window,
+                             softcap=softcap)
         return o.transpose(1, 2).contiguous(), None
-    # fallback: SDPA with a boolean [B, 1, 1|Tq, Tk] mask
+    # fallback: SDPA with a boolean [B, 1, 1|Tq, Tk] mask (with a cap, which SDPA cannot express: the
+    # fp32 composition with the same mask)
     mask = attention_mask
     if mask is not None and mask.dtype == torch.uint8 and mask.dim() == 2:
         # a decoder batch with padding: SDPA takes one mask, so the causal one (and the window) is folded in
@@ -114,6 +127,12 @@ def _damd_attention(module: nn.Module, query: torch.Tensor, key: torch.Tensor, v
             mask = band
         else:
             mask = mask & band if mask.dtype == torch.bool else mask.masked_fill(~band, float("-inf"))
+    if softcap:
+        if mask is None:
+            mask = cached_mask(tq, tk, causal, None, None, query.device)
+        scale = query.shape[-1] ** -0.5 if scaling is None else scaling
+        o = _softcap_attention(query, key, value, float(softcap), mask, dropout if module.training else 0.0, scale)
+        return o.transpose(1, 2).contiguous(), None
     o =torch.nn.functional.scaled_dot_product_attention(query, key, value, attn_mask=mask,
                                                          dropout_p=dropout if module.training else 0.0,
                                                          is_causal=causal and mask is None, scale=scaling,
